@@ -10,6 +10,12 @@ of the same subject (BASELINE config 4: views sharded across GPUs, weak scaling)
 all_gather of the rendered [rays, 5] tiles (asynchronous, awaited one step later; the last one inside the timed region).
 Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last timed step if
+`--dump-outputs DIR` is given (DIR/rgb.npy, depth.npy, acc.npy: what ImportanceRenderer.forward returned, float32; rank 0's
+with N > 1), and the line.  Everything else the script measures or checks (the secondary workloads and precisions, the frames
+overlapped on four streams, the training step, the generator forward, the CPU / stock-ops baselines with the parity protocol,
+the PMC traffic passes, the host's own cost of a step) runs with `--full` only.
+
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its N ranks ITSELF (re-executes under
 torch.distributed.run on 127.0.0.1, one rank per GPU, as the reference spawns its own: sherf/train.py:98-103); launched by a
 torchrun-style launcher it checks --gpus against WORLD_SIZE and refuses a mismatch.
@@ -356,6 +362,12 @@ def main():
                     help='N > 1: views (default, BASELINE config 4: every rank renders its own target view, weak scaling) or rays (ONE frame '
                          'cut into interleaved 1024-ray tiles over the ranks, sherf_amd.dist.ray_tiles: strong scaling, value = the frame\'s '
                          'rays / time); either way one RCCL all_gather of the rendered tiles per step')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run every other measurement and check of this script (the --no-* flags below switch single '
+                         'ones off again); default off: set-up, warm-up, the timed steps, the outputs and the JSON line only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last one returned (rgb [1, R, 3], depth [1, R, 1], acc [1, R, 1]) as DIR/<name>.npy, '
+                         'float32 (rank 0\'s with N > 1)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-torch-gpu-baseline', action='store_true',
                     help='skip timing the oracle (the reference algorithm as stock ATen ops, brute-force K-NN) ON THE GPU over the whole '
@@ -375,6 +387,8 @@ def main():
                          'also at test time (eval_*.sh -> train.py --test_flag -> test(G, ...) with G built .train(), '
                          'training_loop.py:193,311-330); eval = running statistics (G_ema.eval(), training_loop.py:196)')
     a = ap.parse_args()
+    if not a.full:                  # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_torch_gpu_baseline = a.no_secondary = a.no_train = a.no_pmc = True
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ and not (a.torch_gpu_child or a.pmc_child):
         sys.exit(launch_ranks(a.gpus))
@@ -436,6 +450,7 @@ def main():
         torch.cuda.stream = lambda st: contextlib.nullcontext()
     torch.cuda.synchronize(dev)                  # the workload's setup (default stream) is complete before any frame stream starts
     counter = [0]
+    last_out = [None]                # what the last step's ImportanceRenderer.forward returned (rgb, depth, acc)
 
     def step():
         if n_streams == 1:
@@ -446,7 +461,7 @@ def main():
             return frame_on_current_stream(k)
 
     def frame_on_current_stream(k):
-        render_frame(w)
+        last_out[0] = render_frame(w)
         tile = rend.last['out']          # the frame's output buffer as the kernel wrote it: planar [rgb (3R) | depth (R) | acc (R)], no repacking
         if rays_mode and tile.numel() != 5 * n_pad:           # ranks own 1024-ray tiles: equal shard sizes for the gather
             tile = torch.nn.functional.pad(tile, (0, 5 * n_pad - tile.numel()))
@@ -502,6 +517,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_out[0])
     nv = int(rend.last['ws']['counters'][0])
     rank_devices = [str(dev)]
     if world > 1:
@@ -511,7 +528,7 @@ def main():
     gstats = (_ct.c_int64 * 4)()
     if hasattr(_abi.lib(), 'sherf_frame_graph_stats'):
         _abi.call('sherf_frame_graph_stats', gstats, 4)
-    if graphs_on:                                  # the events' pass: see above
+    if graphs_on and a.full:                       # the events' pass: see above
         _abi.call('sherf_profile_frames', 1)
         for _ in range(max(8, min(a.steps, 32))):
             step()
@@ -522,12 +539,14 @@ def main():
     _abi.call('sherf_profile_frames', 0)
     # the HOST's own cost of a step (Python + the native enqueue), measured on an EMPTY queue: in the timed loop above the host runs
     # ahead of the GPU until the queue pushes back, so its wall time there is the GPU's (what `host_per_step_python` used to report)
-    t1 = time.perf_counter()
-    for _ in range(3):
-        step()
-    host_alone = (time.perf_counter() - t1) / 3
-    drain()
-    torch.cuda.synchronize()
+    host_alone = None
+    if a.full:
+        t1 = time.perf_counter()
+        for _ in range(3):
+            step()
+        host_alone = (time.perf_counter() - t1) / 3
+        drain()
+        torch.cuda.synchronize()
     prof = np.array(ms[:n_ms.value * 8], dtype=np.float64).reshape(-1, 8)
     # With frames of several caller streams in flight the HIP events around a launch measure its WALL time, which includes what it cedes to
     # the other frames' kernels -- not the kernel's own cost, and the per-frame timeline is a latency, not a schedule.  The roofline, the
@@ -535,7 +554,7 @@ def main():
     # workload, same box, right after the timed region); in this process they would also be distorted by HIP's mapping of a dozen streams
     # onto four hardware queues (measured: 2.9 instead of 1.7 ms per frame for one frame in flight after a four-stream run).
     prof_overlap, one_frame = None, None
-    if n_streams > 1 and world == 1 and rank == 0 and not a.overlap_child:
+    if n_streams > 1 and world == 1 and rank == 0 and not a.overlap_child and a.full:
         prof_overlap = prof
         one_frame = bench_child(a, lrank, ['--streams', '1', '--steps', str(max(8, min(a.steps, 24))), '--warmup', '6']
                                 + (['--no-secondary'] if a.no_secondary else []))
@@ -591,7 +610,8 @@ def main():
         elif len(prof):
             names = ('host_enqueue', 'smpl_tables_done', 'encoder_done', 'rays_at_encoder_join', 'gather_done', 'mlp_done', 'frame_done')
             res['frame_timeline_ms'] = {k: round(float(v), 4) for k, v in zip(names, prof[:, :7].mean(0))}
-            res['frame_timeline_ms']['host_per_step_python'] = round(1e3 * host_alone, 4)          # Python + native enqueue, empty queue
+            if host_alone is not None:
+                res['frame_timeline_ms']['host_per_step_python'] = round(1e3 * host_alone, 4)      # Python + native enqueue, empty queue
             res['frame_timeline_ms']['host_wall_per_step_in_timed_loop'] = round(1e3 * host_dt / a.steps, 4)   # (includes queue back-pressure)
         if a.overlap_child and len(prof):                   # (child of a one-stream run: throughput + latency with frames overlapping, nothing else)
             res['latency_ms_per_frame'] = round(float(prof[:, 6].mean()), 4)
@@ -719,6 +739,13 @@ def main():
         sys.exit(3)
 
 
+def dump_outputs(path, outs):
+    """DIR/<name>.npy (float32) of what one ImportanceRenderer.forward returned: rgb [1, R, 3], depth [1, R, 1], acc [1, R, 1]."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(('rgb', 'depth', 'acc'), outs):
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def _oracle_state(cfg_name, dev=None):
     """name -> tensor of every renderer / decoder parameter of the configuration's variant (checker side: the oracle's weights)."""
     from oracle import fixtures
@@ -796,6 +823,8 @@ def bench_child(a, lrank, extra, timeout=400):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['LOCAL_RANK'] = str(lrank)
     base = ['--config', a.config, '--precision', a.precision, '--bn-mode', a.bn_mode, '--no-cpu-baseline', '--no-torch-gpu-baseline', '--no-pmc', '--no-train']
+    if getattr(a, 'full', False):                       # (a child of a --full run measures what it did before --full existed)
+        base.append('--full')
     for flag, val in (('--table-precision', a.table_precision), ('--encoder-precision', a.encoder_precision)):
         if val:
             base += [flag, val]

@@ -245,7 +245,7 @@ def test_bench_main_dry_run(cpu_product, monkeypatch, capsys):
     fixtures.CONFIGS['cfg2_ri'] = dict(fixtures.CONFIGS['tiny_nv'], variant='ri')
     try:
         # the default workload: the reference-init network, precision 'auto' (-> one fp16 product), parity = truth protocol + plain 1e-3
-        monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'tiny_ri', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--streams', '1', '--exact-grids'])
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--config', 'tiny_ri', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--streams', '1', '--exact-grids'])
         bench.main()
         res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
         assert res['n_gpus'] == 1 and res['steps'] == 1 and res['unit'] == 'rays/s' and res['value'] > 0
@@ -270,14 +270,14 @@ def test_bench_main_dry_run(cpu_product, monkeypatch, capsys):
         assert par['samples']['sigma_rel_max'] < 1e-3 and par['samples']['rgb_rel_max'] < 1e-3
         assert par['truth']['table']['sigma']['max']['ours_vs_truth'] < 1e-3 and par['image']['psnr_vs_oracle_db'] > 60.0
         # the adversarial workload under f16x3: the truth protocol alone
-        monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'tiny', '--precision', 'f16x3', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--streams', '1',
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--config', 'tiny', '--precision', 'f16x3', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--streams', '1',
                                           '--no-secondary'])
         bench.main()
         res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
         assert res['config']['mlp_precision'] == 'f16x3' and res['parity_ok'] is True and 'plain_ok' not in res['parity']
         assert res['roofline']['kernel'] == 'nerf_mlp_kernel'
         # a precision that misses the tolerance: the JSON line says so and the process exits non-zero
-        monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'tiny', '--precision', 'bf16', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--streams', '1',
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--config', 'tiny', '--precision', 'bf16', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--streams', '1',
                                           '--no-secondary', '--no-pmc'])
         with pytest.raises(SystemExit) as ex:
             bench.main()
@@ -285,6 +285,40 @@ def test_bench_main_dry_run(cpu_product, monkeypatch, capsys):
         assert ex.value.code == 3 and res['parity_ok'] is False and res['parity']['truth_ok'] is False
     finally:
         fixtures.CONFIGS.update(keep)
+
+
+def test_bench_plain_run_dumps_outputs(cpu_product, monkeypatch, capsys, tmp_path):
+    """bench.py without --full: the headline alone (no secondary lines, baselines, parity or training step in the line), and with
+    --dump-outputs DIR the last timed step's rgb / depth / acc as float32 .npy -- identical from run to run on the same arguments,
+    and equal to what ImportanceRenderer.forward returns for that frame."""
+    import json
+    import sys
+    import bench
+    from sherf_amd.renderer import ImportanceRenderer
+    monkeypatch.setattr(torch.Tensor, 'is_cuda', property(lambda self: True))
+    monkeypatch.setattr(bench, '_device', lambda lrank: torch.device('cpu'))
+    monkeypatch.setattr(ImportanceRenderer, '_side', lambda self, dev, idx=0: type('HostStream', (), {'cuda_stream': 8 + 8 * idx})())
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f'run{run}'
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'tiny_ri', '--steps', '2', '--warmup', '1', '--dump-outputs', str(out)])
+        bench.main()
+        res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert res['steps'] == 2 and res['ms_per_step'] > 0 and res['value'] > 0 and res['unit'] == 'rays/s' and res['higher_is_better'] is True
+        assert res['dtype'].startswith('f16 MFMA') and res['metric'].startswith('rendered rays/sec')
+        for key in ('secondary', 'parity', 'parity_ok', 'cpu_baseline', 'torch_gpu_baseline', 'train', 'value_frames_overlapped', 'value_dense'):
+            assert key not in res, key
+        arrs = {n: np.load(out / f'{n}.npy') for n in ('rgb', 'depth', 'acc')}
+        R = res['config']['rays']
+        assert arrs['rgb'].shape == (1, R, 3) and arrs['depth'].shape == (1, R, 1) and arrs['acc'].shape == (1, R, 1)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values()) and arrs['acc'].max() > 0
+        dumps.append(arrs)
+    for n in ('rgb', 'depth', 'acc'):
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    a = bench.argparse.Namespace(config='tiny_ri', precision='f16', bn_mode='train')
+    w = bench.make_workload(a, 0.4, torch.device('cpu'))
+    ref = [t.float().numpy() for t in bench.render_frame(w)]
+    assert all(np.allclose(dumps[0][n], r, rtol=1e-3, atol=1e-4) for n, r in zip(('rgb', 'depth', 'acc'), ref))
 
 
 def test_bench_generator_dry_run(cpu_product, monkeypatch, capsys):
@@ -806,7 +840,6 @@ def test_size_independent_properties_and_rotation(cpu_product):
         P.test_ragged_shapes(5, 7, 2)
 
 
-@pytest.mark.skipif(not os.environ.get('SHERF_SLOW'), reason='BASELINE config 1 (128x128x32) and the per-sample precision sweep on the CPU (~1 min): SHERF_SLOW=1')
 def test_config1_and_per_sample_precision(cpu_product):
     P.test_per_sample_sigma_rgb('f16x3', 1e-3, 1e-3)
     P.test_per_sample_sigma_rgb('bf16', 5e-2, 5e-2)

@@ -632,11 +632,12 @@ def _check_scatter(BX, r, dt, n, P, Hf, Wf, H, W, bnd, d_planes_f, d_feat_f, d_r
     assert rel(d_bias.view(3, 32), dt.sum(0)) < 1e-4
 
 
-@pytest.mark.skipif(not os.environ.get('SHERF_SLOW'), reason='~20 s and covered end to end by tests/test_hipcpu_frame.py: SHERF_SLOW=1 to run the stage in isolation')
-def test_encoder_backward_through_the_real_kernels(cpu_lib, monkeypatch, golden_dir):
-    """sherf_amd/backward_encoder.py: encoder_backward with every entry point served by the CPU build of csrc/bwd_encoder.hip on the
-    full 13-layer encoder of `tiny_nv`, against autograd through the oracle.  (Per-kernel checks + the emulated orchestration run
-    in the default suite; this is their conjunction.)"""
+@pytest.mark.slow           # (~20 s; also covered end to end by tests/test_hipcpu_frame.py)
+def test_encoder_backward_through_the_real_kernels(cpu_lib, svox_lib, monkeypatch, golden_dir):
+    """sherf_amd/backward_encoder.py: encoder_backward with every entry point served by the CPU build of csrc/bwd_encoder.hip (and the
+    input-gradient convolutions by the CPU build of csrc/svox.hip, as in the training step) on the full 13-layer encoder of `tiny_nv`,
+    against autograd through the oracle.  (Per-kernel checks + the emulated orchestration run in the default suite; this is their
+    conjunction.)"""
     from oracle import backward_explicit as BX
     from sherf_amd.backward_encoder import encoder_backward
     from tests.bwd_emulator import make_level
@@ -680,6 +681,10 @@ def test_encoder_backward_through_the_real_kernels(cpu_lib, monkeypatch, golden_
         cap = levels[i + 1]['cap']
         d = torch.zeros(cap, feats.shape[1]); d[:feats.shape[0]] = g[f'stage.level{i}']
         d_levels.append(Mat(d.reshape(-1), cap, feats.shape[1]))
+    def call(name, *a):                      # sherf_svox_conv3_dgrad: the forward's MFMA kernel, host build
+        rc = getattr(svox_lib, name)(*a)
+        assert rc == 0, name
+    monkeypatch.setattr(_lib, 'call', call)
     d_feat, grads = encoder_backward(CpuKernelOps(cpu_lib, monkeypatch), state, ctx, d_levels)
     rel = lambda a, b: float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30))
     assert rel(d_feat.tensor(), g['input.vertex_feat']) < 2e-3

@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout 1800 python bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "[bench rc=$?]"; python -c "
+timeout 1800 python bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/bench_final.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','ms_per_step','roofline','cpu_baseline') if k in d})
 print('timeline', d.get('frame_timeline_ms')); print('parity', json.dumps(d.get('parity'))[:1500]); print('secondary', json.dumps(d.get('secondary'))[:1800]); print('torch', d.get('torch_gpu_baseline'))"

@@ -24,7 +24,7 @@ for k in 1 2 3; do
 done
 wait $PID
 grep "^\[sustain" $L | cut -c1-200
-timeout 900 python bench.py > $OUT/r6a_bench.json 2> $OUT/r6a_bench.err; echo "[bench rc=$?]"; python -c "
+timeout 900 python bench.py --full > $OUT/r6a_bench.json 2> $OUT/r6a_bench.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/r6a_bench.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in list(d)[:12]})
 print('roofline', {k: d['roofline'].get(k) for k in ('kernel','frac','kernel_ms','traffic')}); print('parity_ok', d.get('parity_ok'))

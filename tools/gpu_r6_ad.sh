@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-B="python bench.py --streams 4 --steps 100 --no-secondary --no-train --no-cpu-baseline --no-torch-gpu-baseline --no-pmc"
+B="python bench.py --full --streams 4 --steps 100 --no-secondary --no-train --no-cpu-baseline --no-torch-gpu-baseline --no-pmc"
 for rep in 1 2; do
 for tag in "head" "watch1:SHERF_WATCH_EVERY=1" "pinned:SHERF_MLP_FORM=two_tiles" "both:SHERF_WATCH_EVERY=1 SHERF_MLP_FORM=two_tiles"; do
   name=${tag%%:*}; envs=""; [ "$tag" != "$name" ] && envs=${tag#*:}

@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-for i in 1 2; do timeout 300 python bench.py --no-secondary --no-train --no-cpu-baseline --no-pmc 2>/dev/null | python -c "
+for i in 1 2; do timeout 300 python bench.py --full --no-secondary --no-train --no-cpu-baseline --no-pmc 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('parity_ok'), d['frame_timeline_ms'])"; done
 timeout 2400 python -m pytest tests/test_gpu_parity.py tests/test_gpu_glue.py -m gpu -q -x -p no:cacheprovider 2>&1 | tail -3
 cd /tmp

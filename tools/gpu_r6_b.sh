@@ -12,7 +12,7 @@ timeout 600 python tools/frame_ab.py --config cfg2_dense_ri --arms 0,0 --names e
 echo "[frame_ab rc=$?]"; grep "^\[\|configuration" $OUT/r6b_frame_ab.log | cut -c1-400
 timeout 600 python tools/frame_ab.py --config cfg2_ri --arms 0,0 --names eager,graph --opts "frame_graph=False;frame_graph=True" --rounds 3 > $OUT/r6b_frame_ab_cfg2.log 2>&1
 echo "[frame_ab cfg2_ri rc=$?]"; grep "^\[\|configuration" $OUT/r6b_frame_ab_cfg2.log | cut -c1-400
-timeout 900 python bench.py > $OUT/r6b_bench.json 2> $OUT/r6b_bench.err; echo "[bench rc=$?]"; tail -3 $OUT/r6b_bench.err | cut -c1-300; python -c "
+timeout 900 python bench.py --full > $OUT/r6b_bench.json 2> $OUT/r6b_bench.err; echo "[bench rc=$?]"; tail -3 $OUT/r6b_bench.err | cut -c1-300; python -c "
 import json; d=json.loads(open('$OUT/r6b_bench.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in list(d)[:12]})
 print('roofline', {k: d['roofline'].get(k) for k in ('kernel','frac','kernel_ms','traffic')}); print('parity_ok', d.get('parity_ok'))

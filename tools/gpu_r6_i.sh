@@ -13,7 +13,7 @@ import json; d=json.loads(open('$OUT/r6i_bench_generator.json').read().strip().s
 for k in ('recomputed_every_frame','recomputed_every_frame_backbone_fp16','use_cached_backbone','recomputed_every_frame_eager_producers'):
     print(k, json.dumps(d.get(k))[:600])
 print('graphed', d.get('graphed'))"
-timeout 1500 python bench.py > $OUT/r6i_bench.json 2> $OUT/r6i_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/r6i_bench.err | cut -c1-300; python -c "
+timeout 1500 python bench.py --full > $OUT/r6i_bench.json 2> $OUT/r6i_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/r6i_bench.err | cut -c1-300; python -c "
 import json; d=json.loads(open('$OUT/r6i_bench.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in list(d)[:12]})
 print('roofline', {k: d['roofline'].get(k) for k in ('kernel','frac','kernel_ms','traffic')}); print('parity_ok', d.get('parity_ok'))

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 timeout 1200 python -m pytest tests/test_gpu_parity.py -m gpu -q --no-header -p no:cacheprovider -s > $OUT/a_pytest_parity.log 2>&1; echo "[pytest parity rc=$?]"
 tail -4 $OUT/a_pytest_parity.log | cut -c1-300; grep "^FAILED\|^ERROR\|verdict\|auto ->" $OUT/a_pytest_parity.log | cut -c1-300 | head -20
-timeout 900 python bench.py > $OUT/a_bench.json 2> $OUT/a_bench.err; echo "[bench rc=$?]"; tail -3 $OUT/a_bench.err | cut -c1-300
+timeout 900 python bench.py --full > $OUT/a_bench.json 2> $OUT/a_bench.err; echo "[bench rc=$?]"; tail -3 $OUT/a_bench.err | cut -c1-300
 python - <<PY
 import json
 try:
@@ -18,7 +18,7 @@ try:
     print('auto', d['config'].get('mlp_precision_auto')); print((d.get('parity') or {}).get('table')); print('secondary', json.dumps(d.get('secondary'))[:2500])
 except Exception as e: print('bench parse failed', e)
 PY
-timeout 600 python bench.py --config cfg2 --precision f16x3 --no-secondary --no-cpu-baseline > $OUT/a_bench_adversarial.json 2> $OUT/a_bench_adversarial.err; echo "[bench adversarial rc=$?]"
+timeout 600 python bench.py --full --config cfg2 --precision f16x3 --no-secondary --no-cpu-baseline > $OUT/a_bench_adversarial.json 2> $OUT/a_bench_adversarial.err; echo "[bench adversarial rc=$?]"
 python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --no-header -p no:cacheprovider -s -k "auto or eval_mode or full_size or margin or native" > $OUT/b_pytest.log 2>&1; echo "[pytest rc=$?]"
 tail -3 $OUT/b_pytest.log | cut -c1-300; grep "^FAILED\|^ERROR\|verdict\|auto ->\|clean " $OUT/b_pytest.log | cut -c1-260 | head -30
 timeout 300 python tools/mlp_trace.py --precision f16 --out $OUT/b_mlp_trace_f16.json > $OUT/b_mlp_trace_f16.log 2>&1; echo "[mlp trace rc=$?]"; grep "^\[lib\]\|^\[roofline\]\|^\[trace\]" $OUT/b_mlp_trace_f16.log | cut -c1-200
-timeout 600 python bench.py --no-cpu-baseline > $OUT/b_bench.json 2> $OUT/b_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/b_bench.err | cut -c1-300
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/b_bench.json 2> $OUT/b_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/b_bench.err | cut -c1-300
 python - <<PY
 import json
 try:
@@ -20,7 +20,7 @@ try:
 except Exception as e: print('bench parse failed', e)
 PY
 for V in "SHERF_GATHER_SPLIT=1" "SHERF_GATHER_BRANCHLESS=1" "SHERF_GATHER_BRANCHLESS=128"; do
-  env $V timeout 300 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-secondary --no-pmc 2>/dev/null | python -c "
+  env $V timeout 300 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-secondary --no-pmc 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$V', d['ms_per_step'], d.get('frame_timeline_ms'))"
 done

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --no-header -p no:cacheprovider -s -k "mask_and or warp or deterministic or ragged or rotation or auto or no_valid or full_size" > $OUT/c_pytest.log 2>&1; echo "[pytest rc=$?]"
 tail -3 $OUT/c_pytest.log | cut -c1-300; grep "^FAILED\|^ERROR\|verdict\|auto ->" $OUT/c_pytest.log | cut -c1-260 | head -20
 Q="--steps 40 --warmup 10 --no-cpu-baseline --no-torch-gpu-baseline --no-secondary --no-pmc"
-run() { env $1 timeout 300 python bench.py $Q $2 2>/dev/null | python -c "
+run() { env $1 timeout 300 python bench.py --full $Q $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1 $2', round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s mlp', round(d['roofline']['kernel_ms'],4), d.get('frame_timeline_ms'))"; }
 run X=0 "--streams 1"
@@ -19,7 +19,7 @@ run GPU_MAX_HW_QUEUES=4 "--streams 2"
 run X=0 "--streams 2 --config cfg2_dense_ri"
 run X=0 "--streams 1 --config cfg2_dense_ri"
 run X=0 "--streams 2 --config cfg2 --precision f16x3"
-timeout 600 python bench.py --no-cpu-baseline > $OUT/c_bench.json 2> $OUT/c_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/c_bench.err | cut -c1-300
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/c_bench.json 2> $OUT/c_bench.err; echo "[bench rc=$?]"; tail -2 $OUT/c_bench.err | cut -c1-300
 python - <<PY
 import json
 try:

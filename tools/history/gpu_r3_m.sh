@@ -5,7 +5,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 Q="--steps 40 --warmup 10 --no-cpu-baseline --no-torch-gpu-baseline --no-pmc --no-secondary --precision f16"
-run() { env $1 timeout 300 python bench.py $Q $2 2>/dev/null | python -c "
+run() { env $1 timeout 300 python bench.py --full $Q $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d.get('frame_timeline_ms')
 print('$1 $2', round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s parity_ok', d.get('parity_ok'), t)"; }

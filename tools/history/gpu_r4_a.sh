@@ -13,12 +13,12 @@ timeout 200 python tools/mlp_ab.py --precision f16x3 --config cfg2 --rounds 2 --
 timeout 120 python tools/enc_sp_diag.py tiny_ri > $OUT/a_enc_diag.log 2>&1; echo "[enc diag rc=$?]"; grep -v "^/opt\|Warning" $OUT/a_enc_diag.log | tail -22 | cut -c1-250
 Q="--steps 20 --warmup 5 --no-cpu-baseline --no-torch-gpu-baseline --no-pmc --no-secondary"
 for form in 0 1; do
-  SHERF_MLP_SPLIT=$form timeout 120 python bench.py --config cfg2_ri $Q > $OUT/a_bench_cfg2ri_split$form.json 2> $OUT/a_bench_cfg2ri_split$form.err; echo "[bench cfg2_ri split=$form rc=$?]"
+  SHERF_MLP_SPLIT=$form timeout 120 python bench.py --full --config cfg2_ri $Q > $OUT/a_bench_cfg2ri_split$form.json 2> $OUT/a_bench_cfg2ri_split$form.err; echo "[bench cfg2_ri split=$form rc=$?]"
   python -c "
 import json; d=json.loads(open('$OUT/a_bench_cfg2ri_split$form.json').read().strip().splitlines()[-1])
 print(round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s', {k: (round(v,4) if isinstance(v,float) else v) for k,v in d['roofline'].items() if k in ('kernel_ms','frac','frac_executed')}, d['frame_timeline_ms'])"
 done
-timeout 600 python bench.py > $OUT/a_bench.json 2> $OUT/a_bench.err; echo "[bench default rc=$?]"; python -c "
+timeout 600 python bench.py --full > $OUT/a_bench.json 2> $OUT/a_bench.err; echo "[bench default rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/a_bench.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','ms_per_step','roofline','cpu_baseline','value_cfg2_wide_framing') if k in d})
 print('timeline', d.get('frame_timeline_ms')); print('parity_ok', d.get('parity_ok'), json.dumps(d.get('parity'))[:900]); print('secondary', json.dumps(d.get('secondary'))[:2500]); print('torch', d.get('torch_gpu_baseline'))"

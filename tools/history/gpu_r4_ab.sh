@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 export SHERF_LOCAL_DEVICE=0 SHERF_DIST_BACKEND=gloo SHERF_DIST_TIMEOUT=120
 {
 for part in views rays; do
-  timeout 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 12 --warmup 4 --partition $part --config cfg2_ri > $OUT/ab_bench.json 2> $OUT/ab_bench.err; rc=$?
+  timeout 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 12 --warmup 4 --partition $part --config cfg2_ri > $OUT/ab_bench.json 2> $OUT/ab_bench.err; rc=$?
   echo "[partition $part rc=$rc]"
   python -c "
 import json

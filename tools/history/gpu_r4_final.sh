@@ -5,7 +5,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py > $OUT/r4_bench_final.json 2> $OUT/r4_bench_final.err; echo "[bench rc=$?]"; python -c "
+timeout 900 python bench.py --full > $OUT/r4_bench_final.json 2> $OUT/r4_bench_final.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/r4_bench_final.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','ms_per_step','roofline','cpu_baseline','parity_ok','value_cfg2_wide_framing','ms_per_step_cfg2_wide_framing') if k in d})
 print('config', {k: d['config'].get(k) for k in ('workload','valid_samples','mlp_precision','table_precision','encoder_precision','workspace_bytes','token_capacity','sampler_capacity')})

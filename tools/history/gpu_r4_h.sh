@@ -11,7 +11,7 @@ Q="--steps 20 --warmup 5 --no-cpu-baseline --no-torch-gpu-baseline --no-pmc --no
 for cfg in cfg2_dense_ri cfg2_ri; do
   for enc in f16x3 auto; do
     E=""; [ $enc = f16x3 ] && E="--precision f16 --encoder-precision f16x3"
-    timeout 120 python bench.py --config $cfg $Q $E > $OUT/h_bench_${cfg}_$enc.json 2> $OUT/h_bench_${cfg}_$enc.err; echo "[bench $cfg enc=$enc rc=$?]"
+    timeout 120 python bench.py --full --config $cfg $Q $E > $OUT/h_bench_${cfg}_$enc.json 2> $OUT/h_bench_${cfg}_$enc.err; echo "[bench $cfg enc=$enc rc=$?]"
     python -c "
 import json; d=json.loads(open('$OUT/h_bench_${cfg}_$enc.json').read().strip().splitlines()[-1])
 print(round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s', d['config'].get('mlp_precision'), d['config'].get('table_precision'), d['config'].get('encoder_precision'), {k: (round(v,4) if isinstance(v,float) else v) for k,v in d['roofline'].items() if k in ('kernel_ms','frac','frac_executed')}, d['frame_timeline_ms'], (d['config'].get('mlp_precision_auto') or {}).get('errors_vs_reference_config'))"

@@ -9,7 +9,7 @@ for cfg in cfg2_dense_ri cfg2_ri; do
 done
 Q="--steps 40 --warmup 10 --no-cpu-baseline --no-torch-gpu-baseline --no-pmc --no-secondary --no-train"
 for cfg in cfg2_dense_ri cfg2_ri; do
-    timeout 200 python bench.py --config $cfg $Q > $OUT/n_bench_${cfg}.json 2> $OUT/n_bench_${cfg}.err; echo "[bench $cfg rc=$?]"
+    timeout 200 python bench.py --full --config $cfg $Q > $OUT/n_bench_${cfg}.json 2> $OUT/n_bench_${cfg}.err; echo "[bench $cfg rc=$?]"
     python -c "
 import json; d=json.loads(open('$OUT/n_bench_${cfg}.json').read().strip().splitlines()[-1])
 print(round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s', d['config'].get('mlp_precision'), d['config'].get('table_precision'), d['config'].get('encoder_precision'), {k: (round(v,4) if isinstance(v,float) else v) for k,v in d['roofline'].items() if k in ('kernel_ms','frac','frac_executed')}, d['frame_timeline_ms'], d.get('parity_ok'))"

@@ -9,7 +9,7 @@ Q="--steps 48 --warmup 12 --no-cpu-baseline --no-torch-gpu-baseline --no-pmc --n
 {
 for cfg in cfg2_dense_ri cfg2_ri; do
   for n in 1 4 5 8 4 1; do
-    timeout 200 python bench.py --config $cfg --streams $n $Q > $OUT/u_bench.json 2> $OUT/u_bench.err; rc=$?
+    timeout 200 python bench.py --full --config $cfg --streams $n $Q > $OUT/u_bench.json 2> $OUT/u_bench.err; rc=$?
     python -c "
 import json; d=json.loads(open('$OUT/u_bench.json').read().strip().splitlines()[-1])
 print('$cfg streams $n rc=$rc:', round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'Mrays/s', 'one-in-flight', d.get('ms_per_step_one_frame_in_flight'), 'latency', d.get('latency_ms_per_frame_with_frames_overlapping'), 'mlp', round(d['roofline']['kernel_ms'],4), d['roofline'].get('kernel_ms_with_frames_overlapping'))"
@@ -17,7 +17,7 @@ print('$cfg streams $n rc=$rc:', round(d['ms_per_step'],4), 'ms', round(d['value
 done
 } > $OUT/r4_u.log 2>&1
 cat $OUT/r4_u.log
-timeout 900 python bench.py > $OUT/r4_bench_final.json 2> $OUT/r4_bench_final.err; echo "[bench rc=$?]"; python -c "
+timeout 900 python bench.py --full > $OUT/r4_bench_final.json 2> $OUT/r4_bench_final.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/r4_bench_final.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','ms_per_step','parity_ok','value_one_frame_in_flight','ms_per_step_one_frame_in_flight','latency_ms_per_frame_with_frames_overlapping','value_cfg2_wide_framing','ms_per_step_cfg2_wide_framing','value_cfg2_wide_framing_one_frame_in_flight') if k in d})
 print('roofline', {k: v for k, v in d['roofline'].items() if k in ('frac','kernel_ms','frac_executed','traffic','kernel_ms_with_frames_overlapping')})

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_gpu_glue.py tests/test_gpu_producers.py -q -x -m gpu -k "launch_forms or full_size or whole_generator" > $OUT/r5f_pytest_forms_backbone.txt 2>&1; echo "[pytest forms/backbone rc=$?]"; tail -4 $OUT/r5f_pytest_forms_backbone.txt
 timeout 300 python bench_generator.py --steps 20 --warmup 5 > $OUT/r5f_bench_generator.json 2> $OUT/r5f_bench_generator.err; echo "[bench_generator rc=$?]"; tail -c 2500 $OUT/r5f_bench_generator.json; tail -3 $OUT/r5f_bench_generator.err
 timeout 900 python -m pytest tests/test_gpu_backward.py -q -x -m gpu -s -k "full_size_backward" > $OUT/r5f_pytest_backward_truth64.txt 2>&1; echo "[pytest backward rc=$?]"; grep -v "^$" $OUT/r5f_pytest_backward_truth64.txt | tail -40
-timeout 600 python bench.py --steps 20 --warmup 5 --no-train --no-pmc > $OUT/r5f_bench.json 2> $OUT/r5f_bench.err; echo "[bench rc=$?]"; python - <<'PY'
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-train --no-pmc > $OUT/r5f_bench.json 2> $OUT/r5f_bench.err; echo "[bench rc=$?]"; python - <<'PY'
 import json
 try:
     d = json.loads([l for l in open('/root/repo/gpurun_out/r5f_bench.json') if l.startswith('{')][-1])

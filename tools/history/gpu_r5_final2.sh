@@ -4,7 +4,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py > $OUT/r5_bench_final2.json 2> $OUT/r5_bench_final2.err; echo "[bench rc=$?]"; python -c "
+timeout 900 python bench.py --full > $OUT/r5_bench_final2.json 2> $OUT/r5_bench_final2.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/r5_bench_final2.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in list(d)[:12]})
 print('roofline', {k: d['roofline'].get(k) for k in ('kernel','frac','kernel_ms','frac_executed','traffic','achieved')}); print('parity_ok', d.get('parity_ok'))

@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -m gpu -q --no-header -p no:cacheprovider -s > $OUT/r5_pytest_final3.log 2>&1; echo "[pytest rc=$?]"; tail -4 $OUT/r5_pytest_final3.log | cut -c1-300; grep "^FAILED\|^ERROR" $OUT/r5_pytest_final3.log | cut -c1-300 | head
-timeout 900 python bench.py > $OUT/r5_bench_final3.json 2> $OUT/r5_bench_final3.err; echo "[bench rc=$?]"; python -c "
+timeout 900 python bench.py --full > $OUT/r5_bench_final3.json 2> $OUT/r5_bench_final3.err; echo "[bench rc=$?]"; python -c "
 import json; d=json.loads(open('$OUT/r5_bench_final3.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in list(d)[:12]})
 print('roofline', {k: d['roofline'].get(k) for k in ('kernel','frac','kernel_ms','frac_executed','traffic','achieved')}); print('cpu', d.get('cpu_baseline')); print('parity_ok', d.get('parity_ok'))
