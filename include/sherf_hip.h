@@ -249,8 +249,17 @@ int sherf_mlp_pack_stream(const float* flat, const int32_t* src, int64_t n_slots
  * consumes in step s (-1 = none / padding).  sherf_amd/mlp_pack.py restates it; tests/test_boundary.py compares the two. */
 int sherf_mlp_stream_layout(int prec, int32_t* n_steps, int32_t* step_pieces_host, int32_t* units, int32_t max_steps);
 
+/* The `white_back` argument of every compositing entry point below, and sherf_frame.white_back, is a bit field:
+ *   bit 0  SHERF_COMPOSITE_WHITE_BACK  rendering_options['white_back'] (ray_marcher.py:59-60)
+ *   bit 1  SHERF_COMPOSITE_SOFTPLUS    rendering_options['clamp_mode'] == 'softplus': density = softplus(sigma - 1) as F.softplus evaluates it in
+ *                                      fp32 (ray_marcher.py:37-38); clear: 'relu'
+ * Any other bit is refused with SHERF_EINVAL before anything is launched.  (0 / 1, the values before the mode existed, mean what they meant.) */
+#define SHERF_COMPOSITE_WHITE_BACK 1
+#define SHERF_COMPOSITE_SOFTPLUS 2
+
 /* a15+a16: scatter-back + MipRayMarcher2 (renderer.py:364-371, ray_marcher.py:25-64) on the compact samples;
- * masked-out samples (sigma=-80) contribute exact zeros so they are skipped.  rgb[R][3], depth[R], acc[R]. */
+ * masked-out samples (sigma=-80) contribute exact zeros so they are skipped (under either clamp mode: csrc/composite.hip).
+ * rgb[R][3], depth[R], acc[R]. */
 int sherf_composite_compact(const int32_t* counters, const int32_t* ray_base, const int32_t* ray_cnt,
                             const int32_t* cs_idx, const float* sample_out, const float* ray_d,
                             const float* near, const float* far, int R, int S, int white_back, float* rgb,
@@ -262,9 +271,6 @@ int sherf_composite_compact_cap(int32_t* counters, const int32_t* ray_base, cons
                                 const float* near, const float* far, int R, int S, int white_back, int64_t tok_cap,
                                 float* rgb, float* depth, float* acc, sherf_stream_t stream);
 
-/* MipRayMarcher2.forward on dense inputs (ray_marcher.py:67-70): colors[R][S][3], sigma[R][S], depths[R][S],
- * rays_d[R][3] -> rgb[R][3], depth[R], weights[R][S].  dminmax[2] (device) = global min/max of depths
- * (ray_marcher.py:57). */
 /* Backward of sherf_composite_compact for a loss that reads rgb and acc (BASELINE config 5; the reference's losses do not
  * read the depth map, loss.py:103-176): d_rgb[R][3], d_acc[R] -> d_sample_out[capacity][4] = d/d(rgb, sigma) of every
  * compact sample (autograd of MipRayMarcher2.run_forward, ray_marcher.py:25-64, restricted to the valid samples).
@@ -274,9 +280,20 @@ int sherf_composite_compact_bwd(const int32_t* ray_base, const int32_t* ray_cnt,
                                 int R, int S, int white_back, const float* d_rgb, const float* d_acc,
                                 float* d_sample_out, sherf_stream_t stream);
 
+/* MipRayMarcher2.forward on dense inputs (ray_marcher.py:67-70): colors[R][S][3], sigma[R][S], depths[R][S],
+ * rays_d[R][3] -> rgb[R][3], depth[R], weights[R][S].  dminmax[2] (device) = global min/max of depths
+ * (ray_marcher.py:57). */
 int sherf_composite_dense(const float* colors, const float* sigma, const float* depths, const float* rays_d,
                           int R, int S, int white_back, const float* dminmax, float* rgb, float* depth,
                           float* weights, sherf_stream_t stream);
+/* Backward of sherf_composite_dense w.r.t. colors and sigma (autograd of MipRayMarcher2.run_forward, ray_marcher.py:44-62, incl. the 1e-10 of the
+ * transmittance factor, white_back, the * 2 - 1 and the depth quotient): the forward's inputs + d_rgb[R][3], d_depth[R], d_weights[R][S] (each may
+ * be NULL = zero) -> d_colors[R][S][3], d_sigma[R][S] (raw sigma, through the clamp mode's derivative).  A ray whose depth was replaced by
+ * nan_to_num or moved by the global clamp takes no depth gradient.  No gradient w.r.t. depths / rays_d. */
+int sherf_composite_dense_bwd(const float* colors, const float* sigma, const float* depths, const float* rays_d,
+                              int R, int S, int white_back, const float* dminmax, const float* d_rgb,
+                              const float* d_depth, const float* d_weights, float* d_colors, float* d_sigma,
+                              sherf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a11: sparse voxel encoder (SparseConvNet, renderer.py:708-871; spconv 2.3.3 semantics restated in
@@ -434,7 +451,7 @@ typedef struct {
     const sherf_svox_plan* vox_plan; const int32_t* vox_coord; const float* vox_feat; int32_t vox_n, vox_training;
     /* MLP + compositing (a13-a16) */
     const void* wstream; const float* wbias; int32_t mlp_prec, mlp_parts; float* sample_out;   /* mlp_parts 2..8: gather + network in that many parts on two streams (sherf_nerf_mlp_part); 0, 1: whole */
-    int32_t white_back;
+    int32_t white_back;         /* bit field: SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS (part of the frame graph's key like every other field) */
     int32_t main_after_layer;   /* scheduling: -1 = both streams start at once; k >= 0 = the ray side starts once encoder
                                  * layer k is done (the encoder's small launches are slowed 3-5x by a co-running sampler) */
     float* rgb; float* depth; float* acc;

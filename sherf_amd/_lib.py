@@ -80,6 +80,18 @@ class Frame(ctypes.Structure):                        # sherf_frame
 _STRUCTS = (VoxLevel, SvoxLevelWs, SvoxLayer, SvoxPlan, Frame)
 
 
+# the `white_back` bit field of the compositing entry points and of sherf_frame (include/sherf_hip.h: SHERF_COMPOSITE_*)
+COMPOSITE_WHITE_BACK, COMPOSITE_SOFTPLUS = 1, 2
+CLAMP_MODES = ('relu', 'softplus')
+
+
+def composite_bits(white_back, clamp_mode='relu'):
+    """rendering_options' white_back / clamp_mode -> the entry points' `white_back` argument."""
+    if clamp_mode not in CLAMP_MODES:                 # ray_marcher.py:41-42: `assert False` with this message
+        raise AssertionError("MipRayMarcher only supports `clamp_mode`=`softplus`!")
+    return (COMPOSITE_WHITE_BACK if white_back else 0) | (COMPOSITE_SOFTPLUS if clamp_mode == 'softplus' else 0)
+
+
 _SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
             'sherf_stream_t': ctypes.c_void_p}
 

@@ -21,12 +21,13 @@ from .backward_encoder import encoder_backward
 from .backward_taps import taps_backward
 
 
-def composite_backward(renderer, d_rgb, d_acc, ray_directions, near, far, white_back=False):
+def composite_backward(renderer, d_rgb, d_acc, ray_directions, near, far, white_back=False, clamp_mode='relu'):
     """Gradient of the loss w.r.t. the per-sample (rgb, sigma) produced by the last `renderer.forward` call.
 
     d_rgb [1,R,3], d_acc [1,R,1] (or [R,3] / [R]): gradients w.r.t. the outputs of ImportanceRenderer.forward; the ray
     tensors are the ones that call was given.  Returns [Nv, 4] in the compact sample order of the forward
-    (renderer.last['ws']['cs_idx']): columns dL/d rgb (3), dL/d sigma (raw, pre-ReLU)."""
+    (renderer.last['ws']['cs_idx']): columns dL/d rgb (3), dL/d sigma (raw: before the clamp mode's relu / softplus(sigma - 1),
+    which must be the mode that forward rendered under)."""
     last = renderer.last
     if last is None:
         raise RuntimeError('composite_backward needs the workspace of a preceding forward call')
@@ -38,7 +39,7 @@ def composite_backward(renderer, d_rgb, d_acc, ray_directions, near, far, white_
     # capacity = R x S rows -- a 268 MB zero fill per step at 512 x 512 x 64 for 12 MB of gradient
     out = torch.zeros(max(nv, 1), 4, device=ws['sample_out'].device)
     _lib.call('sherf_composite_compact_bwd', P(ws['ray_base']), P(ws['ray_cnt']), P(ws['cs_idx']), P(ws['sample_out']),
-              P(f32(ray_directions, R, 3)), P(f32(near, R)), P(f32(far, R)), R, S, 1 if white_back else 0,
+              P(f32(ray_directions, R, 3)), P(f32(near, R)), P(f32(far, R)), R, S, _lib.composite_bits(white_back, clamp_mode),
               P(f32(d_rgb, R, 3)), P(f32(d_acc, R)), P(out), _lib.stream())
     return out[:nv]
 
@@ -56,7 +57,7 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
     state.update({'decoder.' + k: v for k, v in decoder.state_dict().items()})
     ops = HipOps()
     # ---- a16 ----
-    d_sample = composite_backward(renderer, d_rgb, d_acc, b['ray_d'], b['near'], b['far'], b['white_back']).contiguous()
+    d_sample = composite_backward(renderer, d_rgb, d_acc, b['ray_d'], b['near'], b['far'], b['white_back'], b.get('clamp_mode', 'relu')).contiguous()
     n = d_sample.shape[0]
     if n == 0:
         raise RuntimeError('render_backward: no valid sample in the last frame')

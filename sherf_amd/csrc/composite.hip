@@ -7,16 +7,44 @@
 // Samples the shell mask rejected carry (rgb 0, sigma -80) in the reference (renderer.py:364-368): relu makes
 // alpha exactly 0, the transmittance factor is fl(1+1e-10) == 1 and the weight is 0, so skipping them is exact.
 // The compact kernel therefore walks only a ray's valid samples (ascending k): HBM-bound, 20 B/ray out.
+//
+// clamp_mode 'softplus' (ray_marcher.py:37-38): the density is softplus(sigma - 1) as F.softplus evaluates it in fp32 (beta 1, threshold 20):
+//   x = sigma - 1;  s = x > 20 ? x : log1pf(expf(x));  ds/dsigma = x > 20 ? 1 : z / (z + 1), z = expf(x)  (autograd's softplus backward;
+//   no sigma > 0 mask: every valid sample receives a density gradient).
+// Skipping the rejected samples stays exact: softplus(-80 - 1) ~ 6.6e-36; times the largest delta (1e10 |d|) that is ~1e-25 |d|, expf of its
+// negative rounds to 1 for every |d| < ~1e17, so alpha is exactly 0, the transmittance factor is fl(1 + 1e-10) == 1 and the weight is 0 -- the
+// same three facts as under relu (tests/test_gpu_softplus.py compares the dense and the compact kernel bit for bit on a scattered frame).
+// The mode travels in bit 1 of the `white_back` argument of every entry point (bit 0: white background; include/sherf_hip.h,
+// SHERF_COMPOSITE_*); each kernel is a template on it, and the relu instantiations are the code these kernels were before.
 #include "common.h"
 
 namespace {
+
+enum { CLAMP_RELU = 0, CLAMP_SOFTPLUS = 1 };
+
+// the density activation of ray_marcher.py:37-40
+template <int MODE>
+__device__ __forceinline__ float density(float sigma) {
+    if (MODE == CLAMP_RELU) return fmaxf(sigma, 0.f);
+    const float x = sigma - 1.f;
+    return x > 20.f ? x : log1pf(expf(x));
+}
+
+// d density / d sigma (threshold_backward / softplus_backward)
+template <int MODE>
+__device__ __forceinline__ float density_grad(float sigma) {
+    if (MODE == CLAMP_RELU) return sigma > 0.f ? 1.f : 0.f;
+    const float x = sigma - 1.f;
+    const float z = expf(x);
+    return x > 20.f ? 1.f : z / (z + 1.f);
+}
 
 __device__ __forceinline__ float depth_at(float near, float range, int k, int S) {
     float step = __fdiv_rn((float)k, (float)(S - 1));
     return __fadd_rn(near, __fmul_rn(step, range));
 }
 
-template <int BATCH>
+template <int BATCH, int MODE>
 __global__ void __launch_bounds__(256) composite_compact_kernel(const int32_t* __restrict__ counters,
                                                                 const int32_t* __restrict__ ray_base,
                                                                 const int32_t* __restrict__ ray_cnt,
@@ -61,7 +89,7 @@ __global__ void __launch_bounds__(256) composite_compact_kernel(const int32_t* _
             const float4 o = oo[j];
             const float t = depth_at(nr, range, k, S);
             const float delta = (k == S - 1 ? 1e10f : depth_at(nr, range, k + 1, S) - t) * dn;
-            const float alpha = 1.f - expf(-(fmaxf(o.w, 0.f) * delta));
+            const float alpha = 1.f - expf(-(density<MODE>(o.w) * delta));
             const float w = alpha * T;
             T = T * (1.f - alpha + 1e-10f);
             cr += w * o.x; cg += w * o.y; cb += w * o.z; wsum += w; dsum += w * t;
@@ -76,6 +104,7 @@ __global__ void __launch_bounds__(256) composite_compact_kernel(const int32_t* _
     acc[r] = wsum;
 }
 
+template <int MODE>
 __global__ void __launch_bounds__(256) composite_dense_kernel(const float* __restrict__ colors, const float* __restrict__ sigma,
                                                               const float* __restrict__ depths, const float* __restrict__ rays_d,
                                                               int R, int S, int white_back, const float* __restrict__ dminmax,
@@ -93,7 +122,7 @@ __global__ void __launch_bounds__(256) composite_dense_kernel(const float* __res
     for (int k = 0; k < S; ++k) {
         const float t = tt[k];
         const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
-        const float alpha = 1.f - expf(-(fmaxf(sg[k], 0.f) * delta));
+        const float alpha = 1.f - expf(-(density<MODE>(sg[k]) * delta));
         const float w = alpha * T;
         T = T * (1.f - alpha + 1e-10f);
         weights[(size_t)r * S + k] = w;
@@ -112,9 +141,10 @@ __global__ void __launch_bounds__(256) composite_dense_kernel(const float* __res
 //   g_w[k] = g_c . c_k + dL/dacc - white_back * sum(g_c):
 //   dL/dc_k     = g_c w_k
 //   dL/dalpha_k = g_w[k] T_k - (sum_{m>k} g_w[m] w_m) / (1 - alpha_k + 1e-10)        (T_m carries the factor of sample k)
-//   dL/dsigma_k = dL/dalpha_k * delta_k * exp(-sigma_k delta_k) * [sigma_k > 0]
+//   dL/dsigma_k = dL/dalpha_k * delta_k * exp(-s_k delta_k) * ds_k/dsigma_k,   s = relu(sigma): [sigma_k > 0];  s = softplus(sigma - 1): z / (z + 1)
 // Two forward sweeps over the ray's compact samples: the first takes the total of g_w w, the second rebuilds T, alpha, w
 // and turns the running prefix into the suffix sum.  Same thread-per-ray shape and traffic class as the forward.
+template <int MODE>
 __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_t* __restrict__ ray_base, const int32_t* __restrict__ ray_cnt,
                                                                     const int32_t* __restrict__ cs_idx, const float4* __restrict__ sample_out,
                                                                     const float* __restrict__ ray_d, const float* __restrict__ near,
@@ -135,7 +165,7 @@ __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_
         const float4 o = sample_out[base + i];
         const float t = depth_at(nr, range, k, S);
         const float delta = (k == S - 1 ? 1e10f : depth_at(nr, range, k + 1, S) - t) * dn;
-        const float alpha = 1.f - expf(-(fmaxf(o.w, 0.f) * delta));
+        const float alpha = 1.f - expf(-(density<MODE>(o.w) * delta));
         total += (gx * o.x + gy * o.y + gz * o.z + gconst) * (alpha * T);
         T = T * (1.f - alpha + 1e-10f);
     }
@@ -146,16 +176,82 @@ __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_
         const float4 o = sample_out[base + i];
         const float t = depth_at(nr, range, k, S);
         const float delta = (k == S - 1 ? 1e10f : depth_at(nr, range, k + 1, S) - t) * dn;
-        const float e = expf(-(fmaxf(o.w, 0.f) * delta));
+        const float e = expf(-(density<MODE>(o.w) * delta));
         const float alpha = 1.f - e, w = alpha * T;
         const float gw = gx * o.x + gy * o.y + gz * o.z + gconst;
         prefix += gw * w;
         const float dalpha = gw * T - (total - prefix) / (1.f - alpha + 1e-10f);
-        const float dsigma = o.w > 0.f ? dalpha * delta * e : 0.f;
+        const float dsigma = MODE == CLAMP_RELU ? (o.w > 0.f ? dalpha * delta * e : 0.f) : dalpha * delta * e * density_grad<MODE>(o.w);
         d_sample_out[base + i] = make_float4(gx * w, gy * w, gz * w, dsigma);
         T = T * (1.f - alpha + 1e-10f);
     }
 }
+
+// Backward of composite_dense_kernel (MipRayMarcher2 on dense inputs, all three outputs) w.r.t. colors and sigma.  With g_c = 2 dL/drgb,
+// W = sum w, D = sum w t, depth = D / W and g_d = dL/ddepth where the depth is the quotient itself, 0 where it was replaced (empty ray: 0 / 0 ->
+// nan_to_num) or moved by the global clamp (autograd passes no gradient through either; its quotient then turns that zero into 0 / 0 = NaN on an
+// empty ray -- here the ray's depth term is dropped):
+//   g_w[k]      = g_c . c_k - white_back * sum(g_c) + dL/dw_k + (g_d / W) (t_k - depth)
+//   dL/dc_k     = g_c w_k
+//   dL/dalpha_k = g_w[k] T_k - (sum_{m>k} g_w[m] w_m) / (1 - alpha_k + 1e-10)
+//   dL/dsigma_k = dL/dalpha_k * delta_k * exp(-s_k delta_k) * ds_k/dsigma_k
+// Two forward sweeps, one thread per ray: the first takes W, D and the total of the depth-free part of g_w w; the second rebuilds T, alpha, w and
+// keeps the three running prefixes in the first sweep's order, so that every suffix (total - prefix) is exactly 0 behind the last sample.
+// A null upstream gradient is zero.  No gradient w.r.t. depths / rays_d.
+template <int MODE>
+__global__ void __launch_bounds__(256) composite_dense_bwd_kernel(const float* __restrict__ colors, const float* __restrict__ sigma,
+                                                                  const float* __restrict__ depths, const float* __restrict__ rays_d,
+                                                                  int R, int S, int white_back, const float* __restrict__ dminmax,
+                                                                  const float* __restrict__ d_rgb, const float* __restrict__ d_depth,
+                                                                  const float* __restrict__ d_weights, float* __restrict__ d_colors,
+                                                                  float* __restrict__ d_sigma) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const float dmin = dminmax[0], dmax = dminmax[1];
+    const float d0 = rays_d[r * 3], d1 = rays_d[r * 3 + 1], d2 = rays_d[r * 3 + 2];
+    const float dn = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    const float* c = colors + (size_t)r * S * 3;
+    const float* sg = sigma + (size_t)r * S;
+    const float* tt = depths + (size_t)r * S;
+    const float* dw = d_weights ? d_weights + (size_t)r * S : nullptr;
+    float* dc = d_colors + (size_t)r * S * 3;
+    float* ds = d_sigma + (size_t)r * S;
+    const float gx = d_rgb ? 2.f * d_rgb[r * 3] : 0.f, gy = d_rgb ? 2.f * d_rgb[r * 3 + 1] : 0.f, gz = d_rgb ? 2.f * d_rgb[r * 3 + 2] : 0.f;
+    const float gconst = white_back ? -(gx + gy + gz) : 0.f;
+    float T = 1.f, total = 0.f, wsum = 0.f, dsum = 0.f;
+    for (int k = 0; k < S; ++k) {
+        const float t = tt[k];
+        const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
+        const float alpha = 1.f - expf(-(density<MODE>(sg[k]) * delta));
+        const float w = alpha * T;
+        T = T * (1.f - alpha + 1e-10f);
+        const float base = gx * c[k * 3] + gy * c[k * 3 + 1] + gz * c[k * 3 + 2] + gconst + (dw ? dw[k] : 0.f);
+        total += base * w; wsum += w; dsum += w * t;
+    }
+    const float dep = dsum / wsum;
+    const bool live = d_depth && dep == dep && dep >= dmin && dep <= dmax;
+    const float gdw = live ? d_depth[r] / wsum : 0.f;
+    T = 1.f;
+    float ptotal = 0.f, pw = 0.f, pd = 0.f;
+    for (int k = 0; k < S; ++k) {
+        const float t = tt[k];
+        const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
+        const float e = expf(-(density<MODE>(sg[k]) * delta));
+        const float alpha = 1.f - e, w = alpha * T;
+        const float base = gx * c[k * 3] + gy * c[k * 3 + 1] + gz * c[k * 3 + 2] + gconst + (dw ? dw[k] : 0.f);
+        ptotal += base * w; pw += w; pd += w * t;
+        const float gw = live ? base + gdw * (t - dep) : base;
+        const float suffix = live ? (total - ptotal) + gdw * ((dsum - pd) - dep * (wsum - pw)) : total - ptotal;
+        const float dalpha = gw * T - suffix / (1.f - alpha + 1e-10f);
+        const float dg = density_grad<MODE>(sg[k]);
+        ds[k] = dg == 0.f ? 0.f : dalpha * delta * e * dg;          // (relu: the sigma > 0 mask, as a select -- not 0 * a product that may overflow)
+        dc[k * 3] = gx * w; dc[k * 3 + 1] = gy * w; dc[k * 3 + 2] = gz * w;
+        T = T * (1.f - alpha + 1e-10f);
+    }
+}
+
+// bit 0 of the entry points' `white_back`: white background; bit 1: clamp_mode 'softplus' (include/sherf_hip.h); anything else is refused
+constexpr int kCompositeBits = SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS;
 
 }  // namespace
 
@@ -165,13 +261,19 @@ extern "C" int sherf_composite_compact_cap(int32_t* counters, const int32_t* ray
                                            float* rgb, float* depth, float* acc, sherf_stream_t stream) {
     SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && sample_out && ray_d && near && far && rgb && depth && acc);
     SHERF_CHECK_ARG(R > 0 && S >= 2 && tok_cap > 0);
-    if (sherf_experiment() & (1 << 20))
-        hipLaunchKernelGGL(composite_compact_kernel<1>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
-                           ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, white_back, tok_cap,
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL((composite_compact_kernel<4, CLAMP_SOFTPLUS>), dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
+                           ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, tok_cap,
+                           counters + 3, rgb, depth, acc);
+    else if (sherf_experiment() & (1 << 20))
+        hipLaunchKernelGGL((composite_compact_kernel<1, CLAMP_RELU>), dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
+                           ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, tok_cap,
                            counters + 3, rgb, depth, acc);
     else
-    hipLaunchKernelGGL(composite_compact_kernel<4>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
-                       ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, white_back, tok_cap,
+    hipLaunchKernelGGL((composite_compact_kernel<4, CLAMP_RELU>), dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
+                       ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, tok_cap,
                        counters + 3, rgb, depth, acc);
     SHERF_LAUNCH_CHECK();
 }
@@ -182,8 +284,15 @@ extern "C" int sherf_composite_compact(const int32_t* counters, const int32_t* r
                                        float* depth, float* acc, sherf_stream_t stream) {
     SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && sample_out && ray_d && near && far && rgb && depth && acc);
     SHERF_CHECK_ARG(R > 0 && S >= 2);
-    hipLaunchKernelGGL(composite_compact_kernel<4>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
-                       ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, white_back,
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL((composite_compact_kernel<4, CLAMP_SOFTPLUS>), dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
+                           ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb,
+                           (int64_t)R * S, static_cast<int32_t*>(nullptr), rgb, depth, acc);
+    else
+    hipLaunchKernelGGL((composite_compact_kernel<4, CLAMP_RELU>), dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base,
+                       ray_cnt, cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb,
                        (int64_t)R * S, static_cast<int32_t*>(nullptr), rgb, depth, acc);
     SHERF_LAUNCH_CHECK();
 }
@@ -193,8 +302,31 @@ extern "C" int sherf_composite_dense(const float* colors, const float* sigma, co
                                      float* weights, sherf_stream_t stream) {
     SHERF_CHECK_ARG(colors && sigma && depths && rays_d && dminmax && rgb && depth && weights);
     SHERF_CHECK_ARG(R > 0 && S >= 1);
-    hipLaunchKernelGGL(composite_dense_kernel, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), colors, sigma, depths,
-                       rays_d, R, S, white_back, dminmax, rgb, depth, weights);
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL(composite_dense_kernel<CLAMP_SOFTPLUS>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), colors, sigma, depths,
+                           rays_d, R, S, wb, dminmax, rgb, depth, weights);
+    else
+    hipLaunchKernelGGL(composite_dense_kernel<CLAMP_RELU>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), colors, sigma, depths,
+                       rays_d, R, S, wb, dminmax, rgb, depth, weights);
+    SHERF_LAUNCH_CHECK();
+}
+
+extern "C" int sherf_composite_dense_bwd(const float* colors, const float* sigma, const float* depths, const float* rays_d,
+                                         int R, int S, int white_back, const float* dminmax, const float* d_rgb,
+                                         const float* d_depth, const float* d_weights, float* d_colors, float* d_sigma,
+                                         sherf_stream_t stream) {
+    SHERF_CHECK_ARG(colors && sigma && depths && rays_d && dminmax && d_colors && d_sigma);
+    SHERF_CHECK_ARG(R > 0 && S >= 1);
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL(composite_dense_bwd_kernel<CLAMP_SOFTPLUS>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), colors, sigma,
+                           depths, rays_d, R, S, wb, dminmax, d_rgb, d_depth, d_weights, d_colors, d_sigma);
+    else
+        hipLaunchKernelGGL(composite_dense_bwd_kernel<CLAMP_RELU>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), colors, sigma,
+                           depths, rays_d, R, S, wb, dminmax, d_rgb, d_depth, d_weights, d_colors, d_sigma);
     SHERF_LAUNCH_CHECK();
 }
 
@@ -204,8 +336,15 @@ extern "C" int sherf_composite_compact_bwd(const int32_t* ray_base, const int32_
                                            float* d_sample_out, sherf_stream_t stream) {
     SHERF_CHECK_ARG(ray_base && ray_cnt && cs_idx && sample_out && ray_d && near && far && d_rgb && d_acc && d_sample_out);
     SHERF_CHECK_ARG(R > 0 && S >= 2);
-    hipLaunchKernelGGL(composite_compact_bwd_kernel, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), ray_base, ray_cnt, cs_idx,
-                       reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, white_back, d_rgb, d_acc,
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL(composite_compact_bwd_kernel<CLAMP_SOFTPLUS>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), ray_base, ray_cnt,
+                           cs_idx, reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, d_rgb, d_acc,
+                           reinterpret_cast<float4*>(d_sample_out));
+    else
+    hipLaunchKernelGGL(composite_compact_bwd_kernel<CLAMP_RELU>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), ray_base, ray_cnt, cs_idx,
+                       reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, d_rgb, d_acc,
                        reinterpret_cast<float4*>(d_sample_out));
     SHERF_LAUNCH_CHECK();
 }

@@ -437,6 +437,7 @@ extern "C" int sherf_frame_graph_stats(int64_t* stats_host, int32_t n) {
 extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
                                   sherf_stream_t stream_side, sherf_stream_t stream_aux) {
     SHERF_CHECK_ARG(f && levels && ((phase & 3) || phase == 4) && stream_side != stream_main && (!stream_aux || (stream_aux != stream_main && stream_aux != stream_side)));
+    SHERF_CHECK_ARG((f->white_back & ~(SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS)) == 0);
     std::lock_guard<std::mutex> frame_lock(g_frame_mu);
     if (g_graph_on < 0) {
         const char* e = getenv("SHERF_FRAME_GRAPH");

@@ -516,9 +516,23 @@ class ImportanceRenderer(nn.Module):
         # (train-mode BatchNorm normalises with batch statistics and MOVES the running ones every frame: parameters only there)
         enc = self.encoder_3d
         pk = enc.__dict__.get('_key_memo') or state_key(fast_params(enc))
+        # (and the density activation the candidates were scored under: _calibrate; a choice is kept per clamp mode, _auto_for_mode)
+        mode = (self.__dict__.get('_clamp_mode', 'relu'),)
         if enc.training:
-            return (True,) + pk
-        return (False,) + pk + state_key([b for m in enc.modules() for b in m._buffers.values() if b is not None])
+            return (True,) + mode + pk
+        return (False,) + mode + pk + state_key([b for m in enc.modules() for b in m._buffers.values() if b is not None])
+
+    _AUTO_STATE = ('auto', 'auto_key', 'auto_frames', 'auto_tripped')
+
+    def _auto_for_mode(self, wc):
+        """The calibrated choice belongs to the clamp mode it was measured under: when the frame's mode differs from the one the weight cache
+        holds a choice for, that choice is put aside and the other mode's (or none) taken up -- a renderer used under both modes calibrates each once."""
+        mode, held = self.__dict__.get('_clamp_mode', 'relu'), wc.get('auto_mode', 'relu')
+        if mode != held:
+            per = wc.setdefault('auto_per_mode', {})
+            per[held] = {k: wc.get(k) for k in self._AUTO_STATE}
+            wc.update(per.get(mode) or dict.fromkeys(self._AUTO_STATE))
+            wc['auto_mode'] = mode
 
     WATCH_RING = int(os.environ.get('SHERF_WATCH_RING', '4'))      # pinned slots of the read-back ring = frames the host may run ahead when every frame is read back
     WATCH_EVERY = int(os.environ.get('SHERF_WATCH_EVERY', '8'))     # frames between two read-backs of the counters (every frame's flags reach the sticky words on the device meanwhile)
@@ -799,6 +813,7 @@ class ImportanceRenderer(nn.Module):
         if mlp == 'auto':
             self._weights(decoder, dev, 'f16x3')
             wc = self._wcache
+            self._auto_for_mode(wc)
             choice = wc['auto']
             if choice is not None and choice != self.REFERENCE_CONFIG:
                 # a kept cheaper configuration is re-measured when anything it was measured under may have moved: the encoder's weights /
@@ -916,15 +931,18 @@ class ImportanceRenderer(nn.Module):
             _lib.call('sherf_render_frame', _ct.byref(fr), 1, levels, *streams)
             cands.append((cfg, ws['sample_out'].clone()))
         self._set_config(fr, decoder, dev, self.REFERENCE_CONFIG, exact)
+        softplus = bool(int(fr.white_back) & _lib.COMPOSITE_SOFTPLUS)
 
         def decide():
             ref = ws['sample_out']
             nv = int(ws['counters'][0])
             choice, report = self.REFERENCE_CONFIG, {}
             if nv > 0:
-                sig_r = ref[:nv, 3].clamp(min=0)
+                # the density the compositing kernel forms from sigma: relu, or softplus(sigma - 1) (a negative sigma counts there)
+                act = (lambda x: torch.nn.functional.softplus(x - 1)) if softplus else (lambda x: x.clamp(min=0))
+                sig_r = act(ref[:nv, 3])
                 for cfg, out in cands:
-                    e_sig = ((out[:nv, 3].clamp(min=0) - sig_r).abs() / sig_r.clamp(min=1.0)).max()
+                    e_sig = ((act(out[:nv, 3]) - sig_r).abs() / sig_r.clamp(min=1.0)).max()
                     e_rgb = ((out[:nv, :3] - ref[:nv, :3]).abs() / ref[:nv, :3].abs().clamp(min=0.1)).max()
                     e = float(torch.maximum(e_sig, e_rgb))
                     report['mlp %s / tables %s / encoder %s' % cfg] = e
@@ -976,8 +994,9 @@ class ImportanceRenderer(nn.Module):
                                     decoder, ray_origins, ray_directions, near, far, input_data, rendering_options)
         if opts.get('depth_resolution_importance', 0) != 0:
             raise NotImplementedError('importance sampling is unreachable/broken in the reference (renderer.py:376,383)')
-        if opts.get('clamp_mode', 'relu') != 'relu' or opts.get('disparity_space_sampling', False):
-            raise NotImplementedError('only clamp_mode=relu, disparity_space_sampling=False (train.py:330-332)')
+        if opts.get('disparity_space_sampling', False):
+            raise NotImplementedError('only disparity_space_sampling=False (train.py:330-332)')
+        _lib.composite_bits(False, opts.get('clamp_mode', 'relu'))     # 'relu' / 'softplus'; anything else: the reference marcher's assertion (ray_marcher.py:41-42)
         # the state keys of the weights are computed once in this call (see _weights, _auto_state_key, SparseConvNet._pack); plain
         # __dict__ stores: nn.Module.__setattr__ costs more than the walks it would guard
         d, enc = self.__dict__, self.encoder_3d.__dict__
@@ -1001,6 +1020,8 @@ class ImportanceRenderer(nn.Module):
         def f32(t):                                    # (already fp32 and contiguous -- the usual case: no dispatcher round trips)
             return t if (t.dtype is F32 and t.is_contiguous() and not t.requires_grad) else t.detach().to(dtype=F32).contiguous()
         smpl = self._smpl(dev)
+        clamp_mode = opts.get('clamp_mode', 'relu')
+        self.__dict__['_clamp_mode'] = clamp_mode                        # (part of what an `auto` choice was measured under: _auto_state_key)
         cfg, calibrate = self._resolve_config(opts, decoder, dev)
         self.__dict__['_opt_mlp_split'] = opts.get('mlp_split')
         self.__dict__['_opt_mlp_form'] = opts.get('mlp_form')
@@ -1125,7 +1146,7 @@ class ImportanceRenderer(nn.Module):
         # a13-a14: fused transformer + NeRF decoder
         self._set_config(fr, decoder, dev, cfg, exact)
         fr.mlp_parts = int(opts.get('mlp_parts', getattr(self, 'mlp_parts', 0)))
-        fr.white_back = 1 if opts.get('white_back', False) else 0
+        fr.white_back = _lib.composite_bits(opts.get('white_back', False), clamp_mode)     # bit 0: white background, bit 1: softplus
         fr.main_after_layer = int(opts.get('main_after_layer', self.main_after_layer))
         noise = float(opts.get('density_noise', 0) or 0)
         decide = None
@@ -1187,7 +1208,7 @@ class ImportanceRenderer(nn.Module):
                          # handles for the (experimental) backward, sherf_amd/backward.py: references, no copies
                          bwd=dict(planes=planes, obs_feat=obs_input_feature, ray_d=ray_directions, near=near, far=far,
                                   bounds=input_data['t_world_bounds'], vox_min=vox_min.reshape(-1)[:3], vox_sh=[int(v) for v in obs_sp_input['out_sh']],
-                                  coord=vcoord, H=H, W=W, white_back=bool(opts.get('white_back', False))))
+                                  coord=vcoord, H=H, W=W, white_back=bool(opts.get('white_back', False)), clamp_mode=clamp_mode))
         self.last['out'] = out
         return ws['rgb'].view(1, R, 3), ws['depth'].view(1, R, 1), ws['acc'].view(1, R, 1)
 
