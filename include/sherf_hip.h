@@ -199,6 +199,30 @@ int sherf_nerf_mlp(const int32_t* counters, const float* tokens, const float* ex
 /* `prec | SHERF_MLP_NO_TRANSFORMER` in any sherf_nerf_mlp* entry point (and in sherf_frame.mlp_prec): the renderer was built with use_trans = False
  * (renderer.py:261, 427) -- the slot-2 completion and the 3-token transformer are skipped, the decoder reads the fused tokens 0 / 1 as they are. */
 #define SHERF_MLP_NO_TRANSFORMER 256
+/* `prec | SHERF_MLP_OSG_DECODER` in sherf_frame.mlp_prec ONLY (the sherf_nerf_mlp* entry points refuse it): the renderer was built with use_NeRF_decoder = False
+ * (renderer.py:261, 429-430) -- sherf_render_frame runs sherf_osg_decoder (below) where it otherwise runs one of the sherf_nerf_mlp* forms; frame->wstream then points
+ * at that entry point's fp32 weight block, and wbias, zfrag, pefrag, mlp_parts and the SHERF_FRAME_MLP_* form flags are ignored.  The low byte of mlp_prec (the
+ * NeRF network's operand precision) is not read on this path -- the head is fp32; the tables' and the encoder's precisions are frame->flags as before;
+ * SHERF_MLP_NO_TRANSFORMER keeps its meaning.  A null wstream with this bit is SHERF_EINVAL. */
+#define SHERF_MLP_OSG_DECODER 512
+/* a13 + the OSGDecoder (use_NeRF_decoder = False; csrc/osg.hip, fp32 throughout): slot-2 token += W_b . PE5(rgb)[:32] (renderer.py:423-424; ALWAYS, the mean below
+ * reads all three tokens), the 3-token transformer (renderer.py:949-993) unless `flags` bit 0 ("no transformer": use_trans = False) is set, then OSGDecoder.forward
+ * (triplane.py:253-265): mean over the three tokens, FullyConnectedLayer(32, 64), Softplus (beta 1, linear above 20), FullyConnectedLayer(64, 4), sigma = y[0],
+ * rgb = sigmoid(y[1:4]) * 1.002 - 0.001.  Same tokens / extras / counters / out as sherf_nerf_mlp: out[c] = (r, g, b, sigma) for c < min(counters[0], capacity);
+ * rows beyond are not written.  Any other bit of `flags` is refused with SHERF_EINVAL before anything is launched.
+ * `weights`: ONE fp32 block, 16-byte aligned, 3524 floats (+ 8416 with the transformer), gains of the FullyConnectedLayers (weight * lr_mul / sqrt(in), bias *
+ * lr_mul: networks_stylegan2.py) folded in by the packer (sherf_amd/osg_pack.py).  L = 0..3 is a lane of the four that share a sample:
+ *   [0]    wbp [9][8][4 L][4]  wbp[s][o / 4][L][o % 4] = W_b[o][f(L, s)], W_b = the effective reprojection matrix's columns 32..63; f(L, s) = the PE5 feature lane L
+ *                              holds in slot s: angle n = L + 4 (s / 2) = 3 q + a -> 3 + 6 q + a (s even: sin) or 6 + 6 q + a (s odd: cos); s = 8: feature L (the raw
+ *                              colour, L < 3); zero where n > 14, the feature is >= 32 or L = 3 in slot 8
+ *   [1152] h0  [16][8][4 L][4] h0[i][k / 4][L][k % 4] = net.0.weight[16 L + i][k] * gain
+ *   [3200] hb0 [16][4 L]       net.0.bias[16 L + i] * gain
+ *   [3264] h1  [16][4 L][4]    h1[i][L][o] = net.2.weight[o][16 L + i] * gain
+ *   [3520] hb1 [4]             net.2.bias * gain
+ *   [3524] transformer.layers.0 (absent with flags bit 0): 0.fn.norm.weight [32], .bias [32], to_qkv.weight [144][32], to_out.0.weight TRANSPOSED [48][32],
+ *          to_out.0.bias [32], 1.fn.norm.weight [32], .bias [32], net.0.weight [32][32], net.0.bias [32], net.3.weight TRANSPOSED [32][32], net.3.bias [32]. */
+int sherf_osg_decoder(const int32_t* counters, const float* tokens, const float* extras, const float* weights, int flags,
+                      int64_t capacity, float* out, sherf_stream_t stream);
 /* sherf_nerf_mlp on ONE contiguous part of the tile list: the compact tiles are cut into `nparts` parts at multiples of 8 tiles (256
  * samples; the cut is computed on the device from counters[0]) and this launch runs part `part` -- so that part k's network can run on
  * one stream beside part k + 1's sherf_gather_tokens (`mode | part << 8 | nparts << 16`: the same cut) on another.  nparts <= 1: everything. */

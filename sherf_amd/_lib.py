@@ -92,6 +92,10 @@ def composite_bits(white_back, clamp_mode='relu'):
     return (COMPOSITE_WHITE_BACK if white_back else 0) | (COMPOSITE_SOFTPLUS if clamp_mode == 'softplus' else 0)
 
 
+# bits of sherf_frame.mlp_prec beside the precision (include/sherf_hip.h: SHERF_MLP_*)
+MLP_NO_TRANSFORMER, MLP_OSG_DECODER = 256, 512
+
+
 _SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
             'sherf_stream_t': ctypes.c_void_p}
 

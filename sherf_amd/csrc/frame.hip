@@ -286,12 +286,14 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                        (half_tables ? 16 : 0);                                                // mode | 16: fp16 tables
         // Gather and MLP in `nparts` contiguous parts of the tile list, part k's MLP (matrix pipe) on the side stream beside part k + 1's
         // gather (texture addresser) on the main one: the two kernels are bound by different units of the CU (frame->mlp_parts).
-        const int nparts = std::min(((g_sherf_debug >> 16) & 15) ? ((g_sherf_debug >> 16) & 15) : f->mlp_parts, kMaxParts);   // (debug bits 16-19 override: A/B runs)
-        const bool split_form = f->zfrag && (((f->flags & SHERF_FRAME_MLP_SPLIT) != 0) != ((g_sherf_debug & 8192) != 0));
+        // SHERF_MLP_OSG_DECODER: the per-sample network is sherf_osg_decoder (csrc/osg.hip) -- one launch form, no parts, no split, no encodings from the gather
+        const bool osg = (f->mlp_prec & SHERF_MLP_OSG_DECODER) != 0;
+        const int nparts = osg ? 1 : std::min(((g_sherf_debug >> 16) & 15) ? ((g_sherf_debug >> 16) & 15) : f->mlp_parts, kMaxParts);   // (debug bits 16-19 override: A/B runs)
+        const bool split_form = !osg && f->zfrag && (((f->flags & SHERF_FRAME_MLP_SPLIT) != 0) != ((g_sherf_debug & 8192) != 0));
         // SHERF_FRAME_PE_FRAGS (round 6): the gather writes the positional encodings as fp16 operand fragments and the pipelined single-fp16-product
         // network reads them (sherf_gather_tokens_pe -> sherf_nerf_mlp3_pe; bit-identical frames).  Only in the configuration it is built for: fp16
         // tables in the eight-channel gather, one pass, one part, the pipelined form; anything else renders as before.
-        const bool pe_frags = (f->flags & SHERF_FRAME_PE_FRAGS) && f->pefrag && half_tables && (f->mlp_prec & 255) == 2 && (f->flags & SHERF_FRAME_MLP_PIPELINED) &&
+        const bool pe_frags = !osg && (f->flags & SHERF_FRAME_PE_FRAGS) && f->pefrag && half_tables && (f->mlp_prec & 255) == 2 && (f->flags & SHERF_FRAME_MLP_PIPELINED) &&
                               !(g_sherf_debug & (1 << 25)) && !split_form && nparts <= 1 && !(f->gather_split & 7) && !(g_sherf_debug & (2048 | (1 << 29)));
         if (nparts > 1 && !(f->gather_split & 1) && !split_form) {
             SHERF_PROF(3, main);
@@ -338,8 +340,11 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         SHERF_CAP_TRACE("network");
         SHERF_PROF(4, main);
         // debug bit 13 flips the form for A/B runs in one process (a frame without zfrag always takes the one-launch kernel)
-        const bool split = f->zfrag && (((f->flags & SHERF_FRAME_MLP_SPLIT) != 0) != ((g_sherf_debug & 8192) != 0));
-        if (pe_frags)
+        const bool split = split_form;
+        if (osg)
+            SHERF_RUN(sherf_osg_decoder(f->counters, f->tokens, f->extras, static_cast<const float*>(f->wstream), (f->mlp_prec & SHERF_MLP_NO_TRANSFORMER) ? 1 : 0, cap,
+                                        f->sample_out, stream_main));
+        else if (pe_frags)
             SHERF_RUN(sherf_nerf_mlp3_pe(f->counters, f->tokens, f->extras, f->pefrag, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, stream_main));
         else if (split)
             SHERF_RUN(sherf_nerf_mlp_split(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->zfrag,
@@ -438,6 +443,7 @@ extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_lev
                                   sherf_stream_t stream_side, sherf_stream_t stream_aux) {
     SHERF_CHECK_ARG(f && levels && ((phase & 3) || phase == 4) && stream_side != stream_main && (!stream_aux || (stream_aux != stream_main && stream_aux != stream_side)));
     SHERF_CHECK_ARG((f->white_back & ~(SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS)) == 0);
+    SHERF_CHECK_ARG(!(f->mlp_prec & SHERF_MLP_OSG_DECODER) || f->wstream);          // (the OSG weight block: include/sherf_hip.h)
     std::lock_guard<std::mutex> frame_lock(g_frame_mu);
     if (g_graph_on < 0) {
         const char* e = getenv("SHERF_FRAME_GRAPH");

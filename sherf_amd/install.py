@@ -10,6 +10,7 @@ What is rebound (names in the reference's modules; none of its files is edited, 
     training.volumetric_rendering.renderer.ImportanceRenderer, training.triplane.ImportanceRenderer -> sherf_amd.renderer.ImportanceRenderer
     training.triplane.NeRFDecoder                                                                 -> sherf_amd.triplane.NeRFDecoder
     training.triplane.RaySampler                                                                  -> sherf_amd.ray_sampler.RaySampler
+    (training.triplane.OSGDecoder stays the reference's own class: with use_NeRF_decoder=False the hosted renderer reads its net[0] / net[2] duck-typed)
     training.triplane.spconv (only the attribute path `spconv.core.SparseConvTensor`, triplane.py:137) -> sherf_amd.voxel.SparseConvTensor
 
 The reference's `TriPlaneGenerator` class itself keeps running: its `synthesis` (triplane.py:81-172) calls `renderer.projection`,

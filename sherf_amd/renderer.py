@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, mlp_pack
+from . import _lib, mlp_pack, osg_pack
 from .ray_marcher import MipRayMarcher2
 from .voxel import SparseConvNet, SparseConvTensor, pack_conv_weights  # noqa: F401
 
@@ -686,11 +686,64 @@ class ImportanceRenderer(nn.Module):
             tok_bias = torch.cat([br + Wc @ bp[32 * s:32 * s + 32] for s in range(3)]).contiguous().to(device)
             wc = self._wcache = dict(key=key, Wa_t=Wa.t().contiguous().to(device), Wb_t=Wb.t().contiguous().to(device), fold=fold,
                                      tok_bias=tok_bias, streams={}, auto=None, flat=None)
-        if prec not in wc['streams']:
+        if not self.use_NeRF_decoder:
+            # OSG path: ONE fp32 weight block whatever the tables' / encoder's precision (sherf_osg_decoder), cached like the NeRF streams
+            if 'osg' not in wc['streams']:
+                wc['streams']['osg'] = (self._pack_osg(decoder, device), None)
+            prec = 'osg'
+        elif prec not in wc['streams']:
             wc['streams'][prec] = self._pack_stream(decoder, device, prec, wc)
         out = dict(wc)
         out['stream'], out['wbias'] = wc['streams'][prec]
         return out
+
+    @staticmethod
+    def _osg_layers(decoder):
+        """(net.0, net.2) of an OSGDecoder -- this package's or, duck-typed, the reference's own instance (triplane.py:242-251) -- else TypeError."""
+        net = getattr(decoder, 'net', None)
+        try:
+            l0, l2 = net[0], net[2]
+            ok = tuple(l0.weight.shape) == (64, 32) and tuple(l2.weight.shape) == (4, 64) and tuple(l0.bias.shape) == (64,) and tuple(l2.bias.shape) == (4,)
+        except Exception:
+            ok = False
+        if not ok:
+            raise TypeError(f'this renderer was built with use_NeRF_decoder=False and needs an OSGDecoder (net.0: 32 -> 64, net.2: 64 -> 4) as `decoder`, '
+                            f'not {type(decoder).__name__}')
+        return l0, l2
+
+    def _check_decoder(self, decoder):
+        """The `decoder` handed to forward must be of the kind the constructor's use_NeRF_decoder switch selects."""
+        if not self.use_NeRF_decoder:
+            self._osg_layers(decoder)
+        elif not (hasattr(decoder, 'pts_linears') and hasattr(decoder, 'alpha_linear')):
+            raise TypeError(f'this renderer was built with use_NeRF_decoder=True and needs a NeRFDecoder as `decoder`, not {type(decoder).__name__}')
+
+    def _pack_osg(self, decoder, device):
+        """The fp32 weight block of sherf_osg_decoder (include/sherf_hip.h), gathered ON THE DEVICE from the live parameters through osg_pack's index
+        map: W_b of the EFFECTIVE reprojection matrix (switched-off feature branches: zero blocks), the head's two FullyConnectedLayers with their
+        run-time gains folded in (weight_gain / bias_gain of the module where present: networks_stylegan2.py:96-131), the transformer if there is one."""
+        l0, l2 = self._osg_layers(decoder)
+        f = lambda t: t.detach().to(device=device, dtype=torch.float32).reshape(-1)
+        Wr, _ = self._effective_reprojection()
+        flat = [f(Wr[:, 32:64].contiguous())]
+        for l in (l0, l2):
+            flat += [f(l.weight) * float(getattr(l, 'weight_gain', 1.0)), f(l.bias) * float(getattr(l, 'bias_gain', 1.0))]
+        if self.transformer is not None:
+            named = dict(self.transformer.layers[0].named_parameters())
+            flat += [f(named[n]) for n, _, _ in osg_pack.TRANS_PARAMS]
+        flat = torch.cat(flat + [torch.zeros(1, device=device)])                   # (last element: the zero that absent slots read)
+        src, n_flat = osg_pack.block_index(self.transformer is not None)
+        if flat.numel() != n_flat + 1:
+            raise RuntimeError('sherf_amd: parameter shapes do not match the OSG weight block')
+        cache = self.__dict__.setdefault('_pack_index', {})
+        ikey = ('osg', self.transformer is not None, str(device))
+        idx = cache.get(ikey)
+        if idx is None:
+            idx = cache[ikey] = torch.from_numpy(np.where(src >= 0, src, n_flat)).to(device)
+        block = flat[idx].contiguous()
+        if not bool(torch.isfinite(block).all()):
+            raise ValueError('non-finite values in the reprojection / transformer / OSGDecoder weights; the OSG weight block cannot be packed')
+        return block
 
     def feature_branches(self):
         """(1d, 2d, 3d): which feature branches reach the fused tokens -- the constructor's switches read the way run_model's if / elif chain reads
@@ -810,6 +863,10 @@ class ImportanceRenderer(nn.Module):
         training = getattr(self, '_in_autograd', False) or (torch.is_grad_enabled() and getattr(self, 'enable_autograd', False))
         if training:
             return (mlp if mlp != 'auto' else 'f16x3', 'f32', 'f16x3'), False
+        if mlp == 'auto' and not self.use_NeRF_decoder:
+            # OSG path: the head is fp32 whatever the setting; `mlp_precision` only selects the tables' / encoder's precision there, and 'auto' is
+            # the fp32-grade configuration without a calibration frame
+            return self.REFERENCE_CONFIG, False
         if mlp == 'auto':
             self._weights(decoder, dev, 'f16x3')
             wc = self._wcache
@@ -831,15 +888,23 @@ class ImportanceRenderer(nn.Module):
             mlp, t0, e0 = choice
             return (mlp, t0 if tab == 'auto' else tab, e0 if enc == 'auto' else enc), False
         tab = tab if tab != 'auto' else ('f16' if mlp in ('f16', 'bf16') else 'f32')
-        enc = enc if enc != 'auto' else 'f16x3'      # (single-product convolutions only where `auto` has measured them: AUTO_CANDIDATES)
+        # (single-product convolutions only where `auto` has measured them: AUTO_CANDIDATES -- or, on the OSG path, where the caller asked for a
+        #  single-product precision: its head is fp32 in every case, so there the setting is about the tables and the encoder alone)
+        enc = enc if enc != 'auto' else ('f16' if not self.use_NeRF_decoder and mlp in ('f16', 'bf16') else 'f16x3')
         return (mlp, tab, enc), False
 
     def _set_config(self, fr, decoder, dev, cfg, exact):
         """The precision-dependent fields of the frame descriptor: the MLP fragment stream and the table / encoder flags."""
         wc = self._weights(decoder, dev, cfg[0])
         fr.wstream, fr.wbias = _lib.addr(wc['stream']), _lib.addr(wc['wbias'])
-        fr.mlp_prec = MLP_PRECISIONS[cfg[0]] | (0 if self.use_trans else 256)      # SHERF_MLP_NO_TRANSFORMER
+        fr.mlp_prec = MLP_PRECISIONS[cfg[0]] | (0 if self.use_trans else _lib.MLP_NO_TRANSFORMER)
         fr.flags = (1 if exact else 0) | (2 if cfg[1] == 'f16' else 0) | (4 if cfg[2] == 'f16' else 0) | (16 if self.__dict__.get('_opt_report_count') else 0)
+        if not self.use_NeRF_decoder:
+            # OSG path (sherf_osg_decoder): one launch form -- mlp_form / mlp_split / pe_in_gather do not apply and the form tuner never runs
+            fr.mlp_prec |= _lib.MLP_OSG_DECODER
+            fr.zfrag = fr.pefrag = None
+            self.__dict__['_form_auto'] = False
+            return wc
         # the two-launch form of the per-sample network (csrc/mlp.hip: nerf_tokens_kernel + nerf_decoder_kernel, bit-identical results):
         # opt-in.  Measured SLOWER than the one-launch kernel on the MI355X in every precision (f16, 512x512x64: 0.35 vs 0.285 ms at 4 %
         # valid samples, 0.62 vs 0.51 ms at 7.6 %; profiles/r04_call_b_mlp_ablations.txt) -- see csrc/mlp.hip for why
@@ -964,6 +1029,8 @@ class ImportanceRenderer(nn.Module):
         if getattr(self, 'enable_autograd', False) and torch.is_grad_enabled() and not getattr(self, '_in_autograd', False):
             if sum(self.feature_branches()) != 3:
                 raise NotImplementedError('the backward through the HIP kernels covers all three feature branches (use_trans True or False); a renderer with a feature branch switched off is forward-only')
+            if not self.use_NeRF_decoder:
+                raise NotImplementedError('the backward through the HIP kernels covers the NeRF decoder only; the OSG path (use_NeRF_decoder=False: OSGDecoder, sherf_osg_decoder) is forward-only')
             # opt-in training path (BASELINE config 5): the same forward, recorded as one autograd node whose backward runs
             # the HIP backward pipeline (sherf_amd/backward.py; experimental until verified on hardware)
             from .backward import RenderFunction, _named_params
@@ -979,8 +1046,7 @@ class ImportanceRenderer(nn.Module):
                     self.encoder_3d._force_stats_update = False
             return RenderFunction.apply(self, decoder, call, planes, obs_input_feature, canonical_sp_conv_volume.features,
                                         *[p for _, p in _named_params(self, decoder)])
-        if not self.use_NeRF_decoder:
-            raise NotImplementedError('sherf_amd implements use_NeRF_decoder = True (every train_*.sh / eval_*.sh); the OSGDecoder path (triplane.py:242-265) is not built')
+        self._check_decoder(decoder)
         if not ray_origins.is_cuda:
             raise RuntimeError('sherf_amd.ImportanceRenderer runs on the GPU only (no CPU fallback)')
         if ray_origins.shape[0] != 1:

@@ -1,6 +1,7 @@
 """Drop-in counterparts of /root/reference/sherf/training/triplane.py for the hot path:
 
   * `NeRFDecoder`        (triplane.py:267-316)  -- parameter container; its math runs inside sherf_nerf_mlp.
+  * `OSGDecoder`         (triplane.py:242-265)  -- parameter container; its math runs inside sherf_osg_decoder.
   * `TriPlaneGenerator`  (triplane.py:29-236)   -- same constructor / mapping / synthesis / forward signatures and
     output dict; the per-frame glue of `synthesis` (triplane.py:105-137, 150-172, 174-217: per-vertex features,
     voxelisation, image reshapes) feeds the MI355X `ImportanceRenderer`.
@@ -38,6 +39,24 @@ class NeRFDecoder(nn.Module):
 
     def forward(self, *a, **k):
         raise RuntimeError('NeRFDecoder is evaluated inside the fused HIP kernel (sherf_nerf_mlp); '
+                           'pass it to ImportanceRenderer.forward as `decoder`')
+
+
+class OSGDecoder(nn.Module):
+    """triplane.py:242-251: the light EG3D head -- mean over the three tokens, FullyConnectedLayer(n_features, 64), Softplus,
+    FullyConnectedLayer(64, 1 + decoder_output_dim).  Parameter container (net.0 / net.2 weight, bias; FullyConnectedLayer's initialisation and run-time
+    gains, `decoder_lr_mul` included); its math runs inside sherf_osg_decoder."""
+
+    def __init__(self, n_features, options):
+        super().__init__()
+        from .stylegan2 import FullyConnectedLayer
+        self.hidden_dim = 64
+        self.net = nn.Sequential(FullyConnectedLayer(n_features, self.hidden_dim, lr_multiplier=options['decoder_lr_mul']),
+                                 nn.Softplus(),
+                                 FullyConnectedLayer(self.hidden_dim, 1 + options['decoder_output_dim'], lr_multiplier=options['decoder_lr_mul']))
+
+    def forward(self, *a, **k):
+        raise RuntimeError('OSGDecoder is evaluated inside the fused HIP kernel (sherf_osg_decoder); '
                            'pass it to ImportanceRenderer.forward as `decoder`')
 
 
@@ -165,9 +184,10 @@ class TriPlaneGenerator(nn.Module):
             from .stylegan2 import Generator as StyleGAN2Backbone
             self.backbone = StyleGAN2Backbone(z_dim, c_dim, w_dim, img_resolution=256, img_channels=32 * 3, mapping_kwargs=mapping_kwargs,
                                               **synthesis_kwargs)
-        if not use_NeRF_decoder:
-            raise NotImplementedError('OSGDecoder path is unused by SHERF (--use_nerf_decoder True in every script)')
-        self.decoder = NeRFDecoder(32)
+        if not use_NeRF_decoder:                # triplane.py:61-62
+            self.decoder = OSGDecoder(32, {'decoder_lr_mul': rendering_kwargs.get('decoder_lr_mul', 1), 'decoder_output_dim': 3})
+        else:
+            self.decoder = NeRFDecoder(32)
         self.neural_rendering_resolution = 64
         self.rendering_kwargs = rendering_kwargs
         self.use_1d_feature, self.use_2d_feature, self.use_3d_feature = use_1d_feature, use_2d_feature, use_3d_feature
