@@ -30,6 +30,7 @@ def main():
     ap.add_argument('--config', default='cfg2')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)       # two steps under rocprofv3 --pmc: nothing printed
     ap.add_argument('--no-pmc', action='store_true', help='skip the two rocprofv3 --pmc passes that count the tap scatter\'s HBM bytes')
+    ap.add_argument('--osg', action='store_true', help='the generator of the reference\'s constructor defaults: use_NeRF_decoder=False, OSGDecoder (same JSON keys)')
     a = ap.parse_args()
     if a.pmc_child:
         a.steps, a.warmup = 2, 1
@@ -63,16 +64,26 @@ def main():
     from synthdata import fixtures, synth                    # seeded synthetic inputs (not the oracle)
     from sherf_amd import dist as sdist
     from sherf_amd.renderer import ImportanceRenderer
-    from sherf_amd.triplane import NeRFDecoder, TriPlaneGenerator
+    from sherf_amd.triplane import NeRFDecoder, OSGDecoder, TriPlaneGenerator
     from sherf_amd.voxel import SparseConvTensor
     smpl = synth.make_synth_smpl(0)
     fx, d, to = bench.make_inputs(a.config, 0.4 + rank * 2 * np.pi / max(world, 1), dev)
-    rend = ImportanceRenderer(True, True, True, use_trans=True, use_NeRF_decoder=True, smpl=smpl)
-    dec = NeRFDecoder(32)
+    rend = ImportanceRenderer(True, True, True, use_trans=True, use_NeRF_decoder=not a.osg, smpl=smpl)
     variant = fixtures.variant_of(a.config)                  # ('_ri' configurations: the reference-init network, as in bench.py)
-    fixtures.load_seeded_state(rend, 'renderer.', variant); fixtures.load_seeded_state(dec, 'decoder.', variant)
+    fixtures.load_seeded_state(rend, 'renderer.', variant)
+    if a.osg:
+        # the head as its own constructor draws it (triplane.py:242-251), the last layer x 10 as in tools/make_golden_osg.py: unit-variance layers give
+        # |sigma| ~ 1 and an almost empty image
+        torch.manual_seed(1)
+        dec = OSGDecoder(32, {'decoder_lr_mul': 1, 'decoder_output_dim': 3})
+        with torch.no_grad():
+            dec.net[2].weight.mul_(10.0)
+    else:
+        dec = NeRFDecoder(32)
+        fixtures.load_seeded_state(dec, 'decoder.', variant)
     rend.to(dev).train(); dec.to(dev).train()
     rend.enable_autograd = True
+    rend.enable_osg_autograd = a.osg                         # (the OSG backward's own opt-in beside it: INTEGRATION.md)
     gen = TriPlaneGenerator.__new__(TriPlaneGenerator)
     torch.nn.Module.__init__(gen); gen.renderer = rend
     sp_input, _ = gen.prepare_sp_input(d['t_vertices'].float(), gen.canonical_obs_vertices(d))
@@ -184,7 +195,7 @@ def main():
             traffic = None
             under_profiler = any(k.startswith(('ROCPROF', 'ROCP_TOOL')) for k in os.environ)      # (never a counter pass inside somebody else's rocprofv3 run)
             if world == 1 and not a.no_pmc and not under_profiler:
-                t = bench.pmc_traffic(a, lrank, timeout=240, child=[sys.executable, os.path.abspath(__file__), '--pmc-child', '--config', a.config],
+                t = bench.pmc_traffic(a, lrank, timeout=240, child=[sys.executable, os.path.abspath(__file__), '--pmc-child', '--config', a.config] + (['--osg'] if a.osg else []),
                                       keys=('gather_tokens_bwd_runs_kernel',))
                 traffic = t.get('hbm_bytes_per_launch') if isinstance(t, dict) and 'error' not in t else t
             roofline = dict(kernel='gather_tokens_bwd_runs_kernel (the tap scatter of sherf_gather_tokens_bwd_binned; events also cover its bin count / scans / fill)', bound='hbm',
@@ -199,7 +210,7 @@ def main():
                               scaling='weak', vs_baseline=None, dtype='f32 (backward: fp32 kernels, MFMA GEMMs on a three-part bf16 split, MFMA sparse-conv input gradient on a range-scaled fp16 split; forward: f16x3 MFMA)',
                               data='synthetic', final_loss=float(loss), phases_ms=phases,
                               host_ms=dict(zip(('forward', 'backward', 'allreduce_adam'), (1e3 * np.mean(host_t, 0)).tolist())), roofline=roofline,
-                              dist=dist_info, config=dict(workload=f'{a.config}: one view per GPU, stub loss MSE(rgb)+MSE(acc)', rays=R))))
+                              dist=dist_info, config=dict(workload=f'{a.config}{" (OSGDecoder)" if a.osg else ""}: one view per GPU, stub loss MSE(rgb)+MSE(acc)', rays=R))))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

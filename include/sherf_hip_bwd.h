@@ -102,6 +102,24 @@ int sherf_bwd_gelu_bwd(float* d, const float* u, int64_t count, sherf_stream_t s
 int sherf_bwd_rgb_fwd(float* lin, int64_t count, sherf_stream_t stream);
 int sherf_bwd_rgb_bwd(float* d, const float* rgb, int64_t count, sherf_stream_t stream);
 
+/* Backward of the OSGDecoder head (triplane.py:253-265; use_NeRF_decoder = False, forward: sherf_osg_decoder) in ONE launch (csrc/bwd_dense.hip).
+ *   z[n][96] (leading dimension ldz >= 96): the three tokens the head averages -- the transformer's output, or the completed input tokens without one;
+ *   d_sample[n][4]: dL/d(r, g, b, sigma), dense, as sherf_composite_compact_bwd leaves it;
+ *   W0g[64][32], b0g[64], W1g[4][64], b1g[4]: the head's two FullyConnectedLayers with their gains folded in, plain row-major.
+ * Per sample the forward is recomputed in fp32 (m = mean of the tokens, a = W0g m + b0g, h = softplus(a): beta 1, linear above 20, y = W1g h + b1g,
+ * s = sigmoid(y[1..3])), then d_y = (d_sigma, d_rgb * 1.002 s (1 - s)), d_h = W1g^T d_y, d_a = d_h sigmoid(a) (d_h above 20), d_m = W0g^T d_a and
+ *   d_z[n][96] (leading dimension ldd >= 96) = d_m / 3 in each of the three tokens, every row written in full;
+ *   dW0g += sum d_a (x) m, db0g += sum d_a, dW1g += sum d_y (x) h, db1g += sum d_y   (ACCUMULATED: zeroed by the caller).
+ * The grid is capped (max_blocks = 0: the default cap, two workgroups per CU; > 0: at most that many workgroups) and walks the samples grid-stride; a
+ * workgroup keeps its 2372 parameter-gradient sums on chip over all its samples and adds them to the outputs with fp32 atomics once, at its end -- the
+ * summation order is not deterministic.  fp32 VALU with libm's expf / log1pf (fp32 grade), no MFMA.  Rows of z / d_z travel as 16-byte accesses when
+ * both pointers are 16-byte aligned and ldz, ldd are multiples of 4, as dwords otherwise.
+ * SHERF_EINVAL before any launch: a null pointer, n < 0, ldz < 96, ldd < 96, max_blocks < 0.  n == 0: returns 0, launches nothing. */
+int sherf_bwd_osg_head(const float* z, int ldz, const float* d_sample, int64_t n,
+                       const float* W0g, const float* b0g, const float* W1g, const float* b1g,
+                       float* d_z, int ldd, float* dW0g, float* db0g, float* dW1g, float* db1g,
+                       int max_blocks, sherf_stream_t stream);
+
 /* Transpose of sherf_fold_tables (csrc/fold.hip): the gradient d_f of a folded, channel-last table
  * (element [g][pix][o] at g*group_base + pix*pix_stride + o) goes back to the NCHW source: d_in[g*32+c][pix] =
  * sum_o W[o][c] d_f[g][pix][o], and dW[32 o][32 c] += sum d_f (x) in  (dW zeroed by the caller).

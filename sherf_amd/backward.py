@@ -9,7 +9,8 @@ How it is verified:
     from their unchanged source on the CPU (tests/test_hipcpu_kernels.py, tests/test_hipcpu_frame.py) and on the MI355X against the
     reference's gradient fingerprints (tests/test_gpu_backward.py, part of `-m gpu`).
 
-Stages (backward order):  composite  ->  dense (decoder + transformer)  ->  taps / slot fusion  ->  sparse encoder.
+Stages (backward order):  composite  ->  dense (decoder + transformer; NeRFDecoder: backward_dense.py, OSGDecoder: backward_osg.py)  ->  taps / slot fusion
+->  sparse encoder.
 """
 import ctypes
 
@@ -18,6 +19,7 @@ import torch
 from . import _lib
 from .backward_dense import HipOps, Mat, dense_backward
 from .backward_encoder import encoder_backward
+from .backward_osg import head_gains, osg_dense_backward
 from .backward_taps import taps_backward
 
 
@@ -64,7 +66,11 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
     # ---- a13 + a14 ----
     tok, ext = Mat.empty(n, 96, dev), Mat.empty(n, 12, dev)                 # (sherf_bwd_untile writes both in full)
     ops.untile(ws['tokens'], ws['extras'], n, tok, ext)
-    d_tin, grads, dWb_pe = dense_backward(ops, state, tok, ext, Mat(d_sample.view(-1), n, 4), use_trans=getattr(renderer, 'transformer', None) is not None)
+    use_trans = getattr(renderer, 'transformer', None) is not None
+    if renderer.use_NeRF_decoder:
+        d_tin, grads, dWb_pe = dense_backward(ops, state, tok, ext, Mat(d_sample.view(-1), n, 4), use_trans=use_trans)
+    else:                                                                   # OSGDecoder: one fused kernel for the head (backward_osg.py)
+        d_tin, grads, dWb_pe = osg_dense_backward(ops, state, tok, ext, Mat(d_sample.view(-1), n, 4), use_trans, head_gains(decoder))
     # ---- a10-a13 ----
     planes, obs_feat = f32(b['planes']), f32(b['obs_feat'])
     P_, (Hf, Wf) = planes.shape[-1], obs_feat.shape[-2:]
@@ -105,7 +111,8 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
 
 class RenderFunction(torch.autograd.Function):
     """autograd node around ImportanceRenderer.forward: (planes, obs_input_feature, sparse-voxel features, *parameters) ->
-    (rgb, depth, acc).  Opt-in per renderer (`renderer.enable_autograd = True`; `sherf_amd.install()` sets it for the class).
+    (rgb, depth, acc).  Opt-in per renderer (`renderer.enable_autograd = True`; `sherf_amd.install()` sets it for the class; a renderer built with
+    use_NeRF_decoder=False also needs `renderer.enable_osg_autograd = True`: staged).
     The depth output carries no gradient (as in the reference's losses, loss.py:103-176)."""
 
     @staticmethod

@@ -156,6 +156,16 @@ class HipOps:
     def rgb_bwd(self, d, rgb):
         _lib.call_bwd('sherf_bwd_rgb_bwd', self._p(d), self._p(rgb), rgb.rows * rgb.cols, self.st)
 
+    def osg_head(self, z, d_sample, W0g, b0g, W1g, b1g, d_z, dW0g, db0g, dW1g, db1g, max_blocks=0):
+        """Backward of the OSGDecoder head in one launch (sherf_bwd_osg_head): z [n,96], d_sample [n,4] dense -> d_z [n,96]; the four parameter
+        gradients (of the gain-folded weights) ACCUMULATE into dW0g [64,32], db0g [64], dW1g [4,64], db1g [4]."""
+        n = z.rows
+        assert z.cols == 96 and (d_z.rows, d_z.cols) == (n, 96) and (d_sample.rows, d_sample.cols, d_sample.ld) == (n, 4, 4), 'osg_head shapes'
+        for m, (r, c) in ((W0g, (64, 32)), (b0g, (1, 64)), (W1g, (4, 64)), (b1g, (1, 4)), (dW0g, (64, 32)), (db0g, (1, 64)), (dW1g, (4, 64)), (db1g, (1, 4))):
+            assert (m.rows, m.cols) == (r, c) and m.ld == c, ('osg_head parameter shapes', m.rows, m.cols, m.ld)
+        _lib.call_bwd('sherf_bwd_osg_head', self._p(z), z.ld, self._p(d_sample), n, self._p(W0g), self._p(b0g), self._p(W1g), self._p(b1g),
+                      self._p(d_z), d_z.ld, self._p(dW0g), self._p(db0g), self._p(dW1g), self._p(db1g), int(max_blocks), self.st)
+
     def untile(self, tokens_tiled, extras_tiled, n, tok, ext):
         _lib.call_bwd('sherf_bwd_untile', _lib.ptr(tokens_tiled), _lib.ptr(extras_tiled), n, self._p(tok), self._p(ext), self.st)
 
@@ -203,6 +213,124 @@ class HipOps:
         _lib.call_bwd('sherf_bwd_bn_relu_apply', self._p(raw), self._p(bnparam), _lib.ptr(n_rows), raw.rows, raw.cols, self._p(act), self.st)
 
 
+class _Stage:
+    """What dense_backward and backward_osg.osg_dense_backward share: buffer constructors, the Linear forward / backward on the C entry points (gradients
+    collected in `grads` under the reference's parameter names), and the stages in front of / behind the decoder -- the slot-2 completion
+    (complete_tokens), the 3-token transformer's recompute and backward, the rgb encoding's weight gradient (dWb_pe)."""
+    T = 'renderer.transformer.layers.0.'
+
+    def __init__(self, ops, state, n, dev):
+        self.ops, self.state, self.n, self.dev, self.grads = ops, state, n, dev, {}
+
+    def Z(self, r, c):
+        return Mat.zeros(r, c, self.dev)
+
+    def E(self, r, c):                                                # (every E is written in full before it is read)
+        return Mat.empty(r, c, self.dev)
+
+    def EP(self, r, c):                                               # rows padded to whole 16-float blocks (K = 71, 199, 187 operands)
+        return Mat.empty_ld(r, c, (c + 15) // 16 * 16, self.dev)
+
+    def P(self, name):
+        return Mat.of(self.state[name])
+
+    def lin_fwd(self, x, wname, act, out=None, addend=None):
+        ops, state = self.ops, self.state
+        W = self.P(wname + '.weight')                              # [out, in]
+        y = out if out is not None else self.E(x.rows, W.rows)
+        b = self.P(wname + '.bias') if (wname + '.bias') in state else None
+        if addend is not None:
+            ops.gemm_bias_act_add(1, x, W, y, b, act, addend)     # (... and the residual stream the output joins)
+        else:
+            ops.gemm_bias_act(0, 1, x, W, y, b, act)               # (bias + ReLU in the product's store)
+        return y
+
+    def lin_bwd(self, d_out, x, wname, d_in=None, beta=0.0, bias=True, db=None, fuse=None, dgrad=True):
+        """grads of y = x W^T + b; returns d_x (accumulated into d_in with beta).  db: the bias gradient when the caller already has it
+        (relu_mask_colsum sums the columns while it masks).  fuse = dict(mask=, colsum=[, r1_s=, r1_w=]): x came out of a ReLU -- the data gradient
+        is masked by the layer below's activations and its column sums (that layer's bias gradient) are taken in the product's store
+        (ops.gemm_dgrad_fused).  dgrad=False: parameter gradients only."""
+        ops, state, grads = self.ops, self.state, self.grads
+        W = self.P(wname + '.weight')
+        dW = self.E(W.rows, W.cols)
+        ops.gemm(1, 0, d_out, x, dW)
+        grads[wname + '.weight'] = dW.tensor().view(state[wname + '.weight'].shape)          # (dW / db: buffers of their own, nothing else writes them: no copy)
+        if bias and (wname + '.bias') in state:
+            if db is None:
+                db = self.Z(1, W.rows)
+                ops.colsum(d_out, db)
+            grads[wname + '.bias'] = db.tensor().view(-1)
+        if not dgrad:
+            return None
+        dx = d_in if d_in is not None else self.E(d_out.rows, W.cols)
+        if fuse is not None:
+            assert beta == 0.0
+            ops.gemm_dgrad_fused(d_out, W, dx, fuse.get('r1_s'), fuse.get('r1_w'), fuse.get('mask'), fuse.get('colsum'))
+        else:
+            ops.gemm(0, 0, d_out, W, dx, beta)
+        return dx
+
+    def complete_tokens(self, tok, ext):
+        """tokens_in = tok (+ slot 2: PE5(rgb)[:32] Wb^T) -> (tin [n,96], pe_rgb [n,33])."""
+        ops, n = self.ops, self.n
+        Wr = self.state['renderer.conv1d_reprojection.weight'].detach().float()[:, :, 0]
+        Wb = Mat.of(Wr[:, 32:64].contiguous())                          # [32 out, 32 in]
+        pe_rgb = self.E(n, 33)
+        ops.pe(ext.colslice(6, 9), 5, pe_rgb)
+        tin = self.E(n, 96)
+        ops.copy2d(tin, tok)
+        ops.gemm(0, 1, pe_rgb.colslice(0, 32), Wb, tin.colslice(64, 96), 1.0)
+        return tin, pe_rgb
+
+    def transformer_forward(self, tin):
+        """The 3-token pre-norm transformer on tin [n,96] -> its activations (dict; 'z96': the output [n, slot 0 | slot 1 | slot 2])."""
+        ops, n, t, E, P = self.ops, self.n, self.T, self.E, self.P
+        c = {}
+        tin3 = tin.as_rows(3 * n, 32)
+        c['h0'], c['xh0'], c['inv0'] = E(3 * n, 32), E(3 * n, 32), E(3 * n, 1)
+        ops.ln_fwd(tin3, P(t + '0.fn.norm.weight'), P(t + '0.fn.norm.bias'), c['h0'], c['xh0'], c['inv0'])
+        c['qkv'] = E(3 * n, 144)
+        ops.gemm(0, 1, c['h0'], P(t + '0.fn.fn.to_qkv.weight'), c['qkv'])
+        c['att'], c['o'] = E(n, 27), E(3 * n, 48)
+        ops.attn_fwd(c['qkv'].as_rows(n, 432), c['att'], c['o'].as_rows(n, 144))
+        c['y'] = self.lin_fwd(c['o'], t + '0.fn.fn.to_out.0', 0, addend=tin3)          # residual (added in the product's store)
+        c['h1'], c['xh1'], c['inv1'] = E(3 * n, 32), E(3 * n, 32), E(3 * n, 1)
+        ops.ln_fwd(c['y'], P(t + '1.fn.norm.weight'), P(t + '1.fn.norm.bias'), c['h1'], c['xh1'], c['inv1'])
+        c['u'] = self.lin_fwd(c['h1'], t + '1.fn.fn.net.0', 0)
+        c['ge'] = E(3 * n, 32)
+        ops.gelu_fwd(c['u'], c['ge'])
+        z = self.lin_fwd(c['ge'], t + '1.fn.fn.net.3', 0, addend=c['y'])
+        c['z96'] = z.as_rows(n, 96)
+        return c
+
+    def transformer_backward(self, c, d_z):
+        """d_z [n,96] (gradient of the transformer's output) -> d_tin [n,96]; the transformer's parameter gradients go to `grads`."""
+        ops, n, t, E, Z, P, grads = self.ops, self.n, self.T, self.E, self.Z, self.P, self.grads
+        d_out = d_z.as_rows(3 * n, 32)
+        # ---- transformer: out = ge W2^T + b2 + y ----
+        d_ge = self.lin_bwd(d_out, c['ge'], t + '1.fn.fn.net.3')
+        ops.gelu_bwd(d_ge, c['u'])
+        d_h1 = self.lin_bwd(d_ge, c['h1'], t + '1.fn.fn.net.0')
+        d_y, dw, db = E(3 * n, 32), Z(1, 32), Z(1, 32)
+        ops.ln_bwd(d_h1, P(t + '1.fn.norm.weight'), c['xh1'], c['inv1'], d_y, dw, db, addend=d_out)          # (+ the residual branch's gradient)
+        grads[t + '1.fn.norm.weight'], grads[t + '1.fn.norm.bias'] = dw.tensor().view(-1), db.tensor().view(-1)
+        # ---- y = o Wo^T + bo + tokens_in ----
+        d_o = self.lin_bwd(d_y, c['o'], t + '0.fn.fn.to_out.0')
+        d_qkv = E(3 * n, 144)
+        ops.attn_bwd(c['qkv'].as_rows(n, 432), c['att'], d_o.as_rows(n, 144), d_qkv.as_rows(n, 432))
+        d_h0 = self.lin_bwd(d_qkv, c['h0'], t + '0.fn.fn.to_qkv', bias=False)
+        d_tin, dw0, db0 = E(3 * n, 32), Z(1, 32), Z(1, 32)
+        ops.ln_bwd(d_h0, P(t + '0.fn.norm.weight'), c['xh0'], c['inv0'], d_tin, dw0, db0, addend=d_y)
+        grads[t + '0.fn.norm.weight'], grads[t + '0.fn.norm.bias'] = dw0.tensor().view(-1), db0.tensor().view(-1)
+        return d_tin.as_rows(n, 96)
+
+    def dWb_pe(self, d_tin96, pe_rgb):
+        """d_tin[:, 64:96]^T PE5(rgb)[:32]: the slot-2 rgb encoding's share of conv1d_reprojection.weight[:, 32:64]."""
+        out = self.E(32, 32)
+        self.ops.gemm(1, 0, d_tin96.colslice(64, 96), pe_rgb.colslice(0, 32), out)
+        return out.tensor()
+
+
 def dense_backward(ops, state, tok, ext, d_sample, use_trans=True):
     """tok [n,96] (gather output, row-major: slot tokens incl. bias, WITHOUT the slot-2 rgb encoding), ext [n,12]
     (x_c 0:3, v_c 3:6, tapped rgb 6:9), d_sample [n,4] = dL/d(rgb, sigma) per valid sample (compositing backward).
@@ -211,71 +339,14 @@ def dense_backward(ops, state, tok, ext, d_sample, use_trans=True):
     Returns (d_tokens_in Mat [n,96], grads {name: tensor}, dWb_pe [32,32]) where dWb_pe is the contribution of the slot-2
     rgb encoding to conv1d_reprojection.weight[:, 32:64] (the rest of that weight's gradient comes from the tap backward)."""
     n, dev = tok.rows, tok.buf.device
-    Z = lambda r, c: Mat.zeros(r, c, dev)
-    E = lambda r, c: Mat.empty(r, c, dev)                           # (every E below is written in full before it is read)
-    EP = lambda r, c: Mat.empty_ld(r, c, (c + 15) // 16 * 16, dev)   # rows padded to whole 16-float blocks (K = 71, 199, 187 operands)
-    P = lambda name: Mat.of(state[name])
-    grads = {}
-
-    def lin_fwd(x, wname, act, out=None, addend=None):
-        W = P(wname + '.weight')                                   # [out, in]
-        y = out if out is not None else E(x.rows, W.rows)
-        b = P(wname + '.bias') if (wname + '.bias') in state else None
-        if addend is not None:
-            ops.gemm_bias_act_add(1, x, W, y, b, act, addend)     # (... and the residual stream the output joins)
-        else:
-            ops.gemm_bias_act(0, 1, x, W, y, b, act)               # (bias + ReLU in the product's store)
-        return y
-
-    def lin_bwd(d_out, x, wname, d_in=None, beta=0.0, bias=True, db=None, fuse=None, dgrad=True):
-        """grads of y = x W^T + b; returns d_x (accumulated into d_in with beta).  db: the bias gradient when the caller already has it
-        (relu_mask_colsum sums the columns while it masks).  fuse = dict(mask=, colsum=[, r1_s=, r1_w=]): x came out of a ReLU -- the data gradient
-        is masked by the layer below's activations and its column sums (that layer's bias gradient) are taken in the product's store
-        (ops.gemm_dgrad_fused).  dgrad=False: parameter gradients only."""
-        W = P(wname + '.weight')
-        dW = E(W.rows, W.cols)
-        ops.gemm(1, 0, d_out, x, dW)
-        grads[wname + '.weight'] = dW.tensor().view(state[wname + '.weight'].shape)          # (dW / db: buffers of their own, nothing else writes them: no copy)
-        if bias and (wname + '.bias') in state:
-            if db is None:
-                db = Z(1, W.rows)
-                ops.colsum(d_out, db)
-            grads[wname + '.bias'] = db.tensor().view(-1)
-        if not dgrad:
-            return None
-        dx = d_in if d_in is not None else E(d_out.rows, W.cols)
-        if fuse is not None:
-            assert beta == 0.0
-            ops.gemm_dgrad_fused(d_out, W, dx, fuse.get('r1_s'), fuse.get('r1_w'), fuse.get('mask'), fuse.get('colsum'))
-        else:
-            ops.gemm(0, 0, d_out, W, dx, beta)
-        return dx
+    st = _Stage(ops, state, n, dev)
+    Z, E, EP, P, grads, lin_fwd, lin_bwd = st.Z, st.E, st.EP, st.P, st.grads, st.lin_fwd, st.lin_bwd
 
     # ================= forward recompute =================
-    t = 'renderer.transformer.layers.0.'
     if use_trans:
-      Wr = state['renderer.conv1d_reprojection.weight'].detach().float()[:, :, 0]
-      Wb = Mat.of(Wr[:, 32:64].contiguous())                          # [32 out, 32 in]
-      pe_rgb = E(n, 33)
-      ops.pe(ext.colslice(6, 9), 5, pe_rgb)
-      tin = E(n, 96)                                                  # tokens_in = tok (+ slot 2: PE(rgb)[:32] Wb^T)
-      ops.copy2d(tin, tok)
-      ops.gemm(0, 1, pe_rgb.colslice(0, 32), Wb, tin.colslice(64, 96), 1.0)
-      tin3 = tin.as_rows(3 * n, 32)
-      h0, xh0, inv0 = E(3 * n, 32), E(3 * n, 32), E(3 * n, 1)
-      ops.ln_fwd(tin3, P(t + '0.fn.norm.weight'), P(t + '0.fn.norm.bias'), h0, xh0, inv0)
-      qkv = E(3 * n, 144)
-      ops.gemm(0, 1, h0, P(t + '0.fn.fn.to_qkv.weight'), qkv)
-      att, o = E(n, 27), E(3 * n, 48)
-      ops.attn_fwd(qkv.as_rows(n, 432), att, o.as_rows(n, 144))
-      y = lin_fwd(o, t + '0.fn.fn.to_out.0', 0, addend=tin3)          # residual (added in the product's store)
-      h1, xh1, inv1 = E(3 * n, 32), E(3 * n, 32), E(3 * n, 1)
-      ops.ln_fwd(y, P(t + '1.fn.norm.weight'), P(t + '1.fn.norm.bias'), h1, xh1, inv1)
-      u = lin_fwd(h1, t + '1.fn.fn.net.0', 0)
-      ge = E(3 * n, 32)
-      ops.gelu_fwd(u, ge)
-      z = lin_fwd(ge, t + '1.fn.fn.net.3', 0, addend=y)
-      z96 = z.as_rows(n, 96)                                          # [n, slot 0 | slot 1 | slot 2]
+      tin, pe_rgb = st.complete_tokens(tok, ext)
+      trans = st.transformer_forward(tin)
+      z96 = trans['z96']                                              # [n, slot 0 | slot 1 | slot 2]
     else:
       # use_trans = False (renderer.py:261, 427; round 6): the fused tokens go to the decoder as they are -- slots 0 / 1 of the gather's output (slot 2, and with it
       # the rgb encoding's W_b term, is never read)
@@ -353,23 +424,5 @@ def dense_backward(ops, state, tok, ext, d_sample, use_trans=True):
     if not use_trans:
         dWb0 = Z(32, 32)
         return d_z, grads, dWb0.tensor()
-    d_out = d_z.as_rows(3 * n, 32)
-    # ---- transformer: out = ge W2^T + b2 + y ----
-    d_ge = lin_bwd(d_out, ge, t + '1.fn.fn.net.3')
-    ops.gelu_bwd(d_ge, u)
-    d_h1 = lin_bwd(d_ge, h1, t + '1.fn.fn.net.0')
-    d_y, dw, db = E(3 * n, 32), Z(1, 32), Z(1, 32)
-    ops.ln_bwd(d_h1, P(t + '1.fn.norm.weight'), xh1, inv1, d_y, dw, db, addend=d_out)          # (+ the residual branch's gradient)
-    grads[t + '1.fn.norm.weight'], grads[t + '1.fn.norm.bias'] = dw.tensor().view(-1), db.tensor().view(-1)
-    # ---- y = o Wo^T + bo + tokens_in ----
-    d_o = lin_bwd(d_y, o, t + '0.fn.fn.to_out.0')
-    d_qkv = E(3 * n, 144)
-    ops.attn_bwd(qkv.as_rows(n, 432), att, d_o.as_rows(n, 144), d_qkv.as_rows(n, 432))
-    d_h0 = lin_bwd(d_qkv, h0, t + '0.fn.fn.to_qkv', bias=False)
-    d_tin, dw0, db0 = E(3 * n, 32), Z(1, 32), Z(1, 32)
-    ops.ln_bwd(d_h0, P(t + '0.fn.norm.weight'), xh0, inv0, d_tin, dw0, db0, addend=d_y)
-    grads[t + '0.fn.norm.weight'], grads[t + '0.fn.norm.bias'] = dw0.tensor().view(-1), db0.tensor().view(-1)
-    d_tin96 = d_tin.as_rows(n, 96)
-    dWb_pe = E(32, 32)
-    ops.gemm(1, 0, d_tin96.colslice(64, 96), pe_rgb.colslice(0, 32), dWb_pe)
-    return d_tin96, grads, dWb_pe.tensor()
+    d_tin96 = st.transformer_backward(trans, d_z)
+    return d_tin96, grads, st.dWb_pe(d_tin96, pe_rgb)

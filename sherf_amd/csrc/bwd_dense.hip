@@ -384,7 +384,173 @@ __global__ void bn_relu_apply_kernel(const float* __restrict__ raw, const float*
     act[i] = r < *n_rows ? fmaxf(raw[i] * bnparam[c] + bnparam[C + c], 0.f) : 0.f;
 }
 
+// ---- backward of the OSGDecoder head (triplane.py:253-265; forward: csrc/osg.hip) in one launch -- see include/sherf_hip_bwd.h ----
+// Layout.  A workgroup takes 64 samples per trip and walks the samples grid-stride.  Each trip has two phases:
+//   (1) FOUR LANES PER SAMPLE, as the forward.  Lane L of a quad reads float4 words L, L + 4, .. L + 20 of the sample's 96-float row (the quad reads
+//       64 contiguous bytes per load), so it holds channels 4 L .. 4 L + 3 and 16 + 4 L .. 16 + 4 L + 3 of all three tokens: the token mean is lane-local
+//       and reaches the other three lanes through 32 __shfl.  The 64 hidden units are split over the quad, unit 4 i + L in lane L: the forward is
+//       recomputed (a, softplus, y summed over the quad), then d_y, d_h, d_a and the lane's part of d_m = W0^T d_a, summed over the quad; lane L keeps
+//       and stores the eight channels it loaded, for all three tokens.  W0 lies in LDS as [i][k / 4][L][4] (the quad reads four consecutive 16-byte
+//       words: conflict-free, other quads broadcast), W1 as [unit][4].  The sample's d_a[64], h[64], m[32], d_y[4] go to LDS (row stride 68 floats for
+//       d_a / h: the quad's four consecutive units of eight samples fall on 32 different banks).
+//   (2) THE PARAMETER GRADIENTS, every thread over the trip's 64 staged samples: thread t owns dW0[t / 4][8 (t % 4) .. + 8] (one d_a word, two m float4
+//       -- at most four different addresses per instruction, the rest broadcast), dW1[t / 64][t % 64], threads < 64 db0[t], threads < 4 db1[t]:
+//       11 accumulators in registers over ALL trips of the workgroup.
+// At the end the 2372 sums pass through LDS so that every atomic instruction of a wave adds 256 contiguous bytes: one device atomic per parameter per
+// WORKGROUP (the order of the workgroups' adds is not deterministic).  Samples past n take part with d_sample = 0 and a zero row: every product they
+// stage is an exact zero; they store nothing.  fp32 VALU, libm transcendentals (expf, log1pf), no MFMA.
+constexpr int OH_THREADS = 256, OH_SAMPLES = 64, OH_LD = 68;
+constexpr int OH_W0 = 0, OH_B0 = 2048, OH_W1 = 2112, OH_B1 = 2368, OH_PARAMS = 2372;
+
+__device__ __forceinline__ float oh_quad_sum(float v) {
+    v += __shfl_xor(v, 1);
+    return v + __shfl_xor(v, 2);
+}
+
+__global__ void __launch_bounds__(OH_THREADS) osg_head_bwd_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ d_sample, int64_t n,
+                                                                  const float* __restrict__ W0g, const float* __restrict__ b0g,
+                                                                  const float* __restrict__ W1g, const float* __restrict__ b1g, float* __restrict__ d_z,
+                                                                  int ldd, float* __restrict__ dW0g, float* __restrict__ db0g, float* __restrict__ dW1g,
+                                                                  float* __restrict__ db1g, int vec) {
+    __shared__ __attribute__((aligned(16))) float s_w[OH_PARAMS];
+    __shared__ __attribute__((aligned(16))) float s_da[OH_SAMPLES * OH_LD], s_h[OH_SAMPLES * OH_LD], s_m[OH_SAMPLES * 32], s_dy[OH_SAMPLES * 4];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2048; i += OH_THREADS) {                  // slot [i][k / 4][L][k % 4] <- W0g[4 i + L][k]
+        const int e = i & 3, L_ = (i >> 2) & 3, kq = (i >> 4) & 7, ii = i >> 7;
+        s_w[OH_W0 + i] = W0g[(4 * ii + L_) * 32 + 4 * kq + e];
+    }
+    if (tid < 64) s_w[OH_B0 + tid] = b0g[tid];
+    s_w[OH_W1 + tid] = W1g[(tid & 3) * 64 + (tid >> 2)];            // [unit][output]
+    if (tid < 4) s_w[OH_B1 + tid] = b1g[tid];
+    __syncthreads();
+    const float4* w04 = reinterpret_cast<const float4*>(s_w + OH_W0);
+    const float4* w14 = reinterpret_cast<const float4*>(s_w + OH_W1);
+    const int L = tid & 3, qb = (tid & 63) & ~3, s = tid >> 2;
+    const int u0 = tid >> 2, c0 = 8 * (tid & 3), o1 = tid >> 6, u1 = tid & 63;      // phase 2: what this thread accumulates
+    float acc0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, acc1 = 0.f, accb0 = 0.f, accb1 = 0.f;
+    for (int64_t base = (int64_t)blockIdx.x * OH_SAMPLES; base < n; base += (int64_t)gridDim.x * OH_SAMPLES) {      // (uniform over the workgroup)
+        const int64_t c = base + s;
+        const bool live = c < n;
+        // ---- phase 1: this lane's eight channels of the three tokens, their mean ----
+        float mo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float ds0 = 0.f, ds1 = 0.f, ds2 = 0.f, ds3 = 0.f;
+        if (live) {
+            const float* zr = z + c * ldz;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                float4 v;
+                if (vec) v = reinterpret_cast<const float4*>(zr)[4 * q + L];
+                else { const float* p = zr + 4 * (4 * q + L); v = make_float4(p[0], p[1], p[2], p[3]); }
+                const int h_ = 4 * (q & 1);
+                mo[h_] += v.x; mo[h_ + 1] += v.y; mo[h_ + 2] += v.z; mo[h_ + 3] += v.w;
+            }
+            const float* dp = d_sample + c * 4;
+            ds0 = dp[0]; ds1 = dp[1]; ds2 = dp[2]; ds3 = dp[3];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mo[k] *= (1.0f / 3.0f);
+        float m[32];
+#pragma unroll
+        for (int kq = 0; kq < 8; ++kq)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[4 * kq + e] = __shfl(mo[4 * (kq >> 2) + e], qb + (kq & 3));
+        // ---- the forward: units 4 i + L ----
+        float hh[16], sg[16], y1 = 0.f, y2 = 0.f, y3 = 0.f;                   // (sigma = y0 is not needed: its gradient passes through)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            float a = s_w[OH_B0 + 4 * i + L];
+#pragma unroll
+            for (int kq = 0; kq < 8; ++kq) {
+                const float4 w = w04[(i * 8 + kq) * 4 + L];
+                a += w.x * m[4 * kq] + w.y * m[4 * kq + 1] + w.z * m[4 * kq + 2] + w.w * m[4 * kq + 3];
+            }
+            // torch.nn.Softplus(): beta 1, linear above 20; its derivative sigmoid(a), 1 above 20
+            if (a > 20.0f) { hh[i] = a; sg[i] = 1.0f; }
+            else { const float ex = expf(a); hh[i] = log1pf(ex); sg[i] = ex / (1.0f + ex); }
+            const float4 w1 = w14[4 * i + L];
+            y1 += w1.y * hh[i]; y2 += w1.z * hh[i]; y3 += w1.w * hh[i];
+        }
+        y1 = oh_quad_sum(y1) + s_w[OH_B1 + 1]; y2 = oh_quad_sum(y2) + s_w[OH_B1 + 2]; y3 = oh_quad_sum(y3) + s_w[OH_B1 + 3];
+        const float s1 = 1.0f / (1.0f + expf(-y1)), s2 = 1.0f / (1.0f + expf(-y2)), s3 = 1.0f / (1.0f + expf(-y3));
+        const float dy0 = ds3, dy1 = ds0 * 1.002f * s1 * (1.0f - s1), dy2 = ds1 * 1.002f * s2 * (1.0f - s2), dy3 = ds2 * 1.002f * s3 * (1.0f - s3);
+        // ---- back: d_h, d_a, this lane's part of d_m ----
+        float dm[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dm[k] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float4 w1 = w14[4 * i + L];
+            const float da = (w1.x * dy0 + w1.y * dy1 + w1.z * dy2 + w1.w * dy3) * sg[i];
+            s_da[s * OH_LD + 4 * i + L] = da;
+            s_h[s * OH_LD + 4 * i + L] = hh[i];
+#pragma unroll
+            for (int kq = 0; kq < 8; ++kq) {
+                const float4 w = w04[(i * 8 + kq) * 4 + L];
+                dm[4 * kq] += w.x * da; dm[4 * kq + 1] += w.y * da; dm[4 * kq + 2] += w.z * da; dm[4 * kq + 3] += w.w * da;
+            }
+        }
+        float keep[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};    // d_z of the channels this lane loaded (the same for the three tokens)
+#pragma unroll
+        for (int kq = 0; kq < 8; ++kq)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = oh_quad_sum(dm[4 * kq + e]) * (1.0f / 3.0f);
+                if ((kq & 3) == L) keep[4 * (kq >> 2) + e] = t;
+            }
+        if (live) {
+            float* dr = d_z + c * ldd;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const int h_ = 4 * (q & 1);
+                if (vec) reinterpret_cast<float4*>(dr)[4 * q + L] = make_float4(keep[h_], keep[h_ + 1], keep[h_ + 2], keep[h_ + 3]);
+                else { float* p = dr + 4 * (4 * q + L); p[0] = keep[h_]; p[1] = keep[h_ + 1]; p[2] = keep[h_ + 2]; p[3] = keep[h_ + 3]; }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { s_m[s * 32 + 4 * L + e] = mo[e]; s_m[s * 32 + 16 + 4 * L + e] = mo[4 + e]; }
+        if (L == 0) { s_dy[s * 4] = dy0; s_dy[s * 4 + 1] = dy1; s_dy[s * 4 + 2] = dy2; s_dy[s * 4 + 3] = dy3; }
+        __syncthreads();
+        // ---- phase 2: the trip's 64 outer products ----
+#pragma unroll 4
+        for (int r = 0; r < OH_SAMPLES; ++r) {
+            const float da = s_da[r * OH_LD + u0];
+            const float4 ma = *reinterpret_cast<const float4*>(s_m + r * 32 + c0), mb = *reinterpret_cast<const float4*>(s_m + r * 32 + c0 + 4);
+            acc0[0] += da * ma.x; acc0[1] += da * ma.y; acc0[2] += da * ma.z; acc0[3] += da * ma.w;
+            acc0[4] += da * mb.x; acc0[5] += da * mb.y; acc0[6] += da * mb.z; acc0[7] += da * mb.w;
+            acc1 += s_dy[r * 4 + o1] * s_h[r * OH_LD + u1];
+            if (tid < 64) accb0 += s_da[r * OH_LD + tid];
+            if (tid < 4) accb1 += s_dy[r * 4 + tid];
+        }
+        __syncthreads();                                             // (the next trip overwrites the staged samples)
+    }
+    // ---- the workgroup's 2372 sums: through LDS, then one atomic each, 256 contiguous bytes per wave instruction ----
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s_da[OH_W0 + u0 * 32 + c0 + j] = acc0[j];
+    if (tid < 64) s_da[OH_B0 + tid] = accb0;
+    s_da[OH_W1 + o1 * 64 + u1] = acc1;
+    if (tid < 4) s_da[OH_B1 + tid] = accb1;
+    __syncthreads();
+    for (int i = tid; i < OH_PARAMS; i += OH_THREADS) {
+        float* p = i < OH_B0 ? dW0g + i : i < OH_W1 ? db0g + (i - OH_B0) : i < OH_B1 ? dW1g + (i - OH_W1) : db1g + (i - OH_B1);
+        unsafeAtomicAdd(p, s_da[i]);
+    }
+}
+
 }  // namespace
+
+extern "C" int sherf_bwd_osg_head(const float* z, int ldz, const float* d_sample, int64_t n, const float* W0g, const float* b0g, const float* W1g,
+                                  const float* b1g, float* d_z, int ldd, float* dW0g, float* db0g, float* dW1g, float* db1g, int max_blocks,
+                                  sherf_stream_t stream) {
+    SHERF_CHECK_ARG(z && d_sample && W0g && b0g && W1g && b1g && d_z && dW0g && db0g && dW1g && db1g);
+    SHERF_CHECK_ARG(n >= 0 && ldz >= 96 && ldd >= 96 && max_blocks >= 0);
+    if (n == 0) return SHERF_OK;
+    // 53.5 KB of LDS per workgroup: two per CU are resident, and the default grid is exactly those
+    const int64_t blocks = (n + OH_SAMPLES - 1) / OH_SAMPLES, cap = max_blocks > 0 ? max_blocks : 2 * n_cus();
+    const int vec = ((reinterpret_cast<size_t>(z) | reinterpret_cast<size_t>(d_z)) & 15) == 0 && ldz % 4 == 0 && ldd % 4 == 0;      // else dword accesses
+    hipLaunchKernelGGL(osg_head_bwd_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(OH_THREADS), 0, as_stream(stream), z, ldz, d_sample, n,
+                       W0g, b0g, W1g, b1g, d_z, ldd, dW0g, db0g, dW1g, db1g, vec);
+    SHERF_LAUNCH_CHECK();
+}
 
 extern "C" int sherf_bwd_untile(const float* tokens_tiled, const float* extras_tiled, int64_t n, float* tok, float* ext,
                                 sherf_stream_t stream) {

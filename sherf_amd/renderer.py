@@ -328,6 +328,10 @@ _SIDE_STREAMS = {}           # (device, caller stream) -> [side, aux]
 
 
 class ImportanceRenderer(nn.Module):
+    # beside `enable_autograd` (set per instance, or for the class by sherf_amd.install()): a renderer built with use_NeRF_decoder=False records its
+    # grad-enabled forwards for the HIP backward only when this is set too -- the OSG backward is staged
+    enable_osg_autograd = False
+
     def __init__(self, use_1d_feature=True, use_2d_feature=True, use_3d_feature=True, use_trans=False, use_NeRF_decoder=False,
                  smpl=None, smpl_path=os.path.join('assets', 'SMPL_NEUTRAL.pkl'), mlp_precision='auto', table_precision='auto', encoder_precision='auto'):
         super().__init__()
@@ -1029,8 +1033,9 @@ class ImportanceRenderer(nn.Module):
         if getattr(self, 'enable_autograd', False) and torch.is_grad_enabled() and not getattr(self, '_in_autograd', False):
             if sum(self.feature_branches()) != 3:
                 raise NotImplementedError('the backward through the HIP kernels covers all three feature branches (use_trans True or False); a renderer with a feature branch switched off is forward-only')
-            if not self.use_NeRF_decoder:
-                raise NotImplementedError('the backward through the HIP kernels covers the NeRF decoder only; the OSG path (use_NeRF_decoder=False: OSGDecoder, sherf_osg_decoder) is forward-only')
+            if not self.use_NeRF_decoder and not getattr(self, 'enable_osg_autograd', False):
+                raise NotImplementedError('the backward of the OSG path (use_NeRF_decoder=False: OSGDecoder, sherf_osg_decoder / sherf_bwd_osg_head) is staged: '
+                                          'with enable_autograd alone this renderer is forward-only; set enable_osg_autograd = True beside it to train through it')
             # opt-in training path (BASELINE config 5): the same forward, recorded as one autograd node whose backward runs
             # the HIP backward pipeline (sherf_amd/backward.py; experimental until verified on hardware)
             from .backward import RenderFunction, _named_params
