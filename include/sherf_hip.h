@@ -33,6 +33,7 @@ typedef void* sherf_stream_t; /* hipStream_t */
 #define SHERF_V 6890     /* SMPL vertices (renderer.py:584 hard-codes 6890*3) */
 #define SHERF_NJ 24
 #define SHERF_MAX_CELLS (64 * 64 * 64)
+#define SHERF_SHELL_RADIUS 0.05f /* the shell of sherf_sample_mask_nn (renderer.py:318); the smallest cell_size / radius of the cell lists and near lists it reads */
 
 int sherf_version(void);
 const char* sherf_last_error(void);
@@ -76,13 +77,16 @@ int sherf_smpl_c2s_table(const float* weights, const float* A_big, const float* 
  * a6 support: uniform cell list over n (<= 6890) vertices, replacing the brute-force pytorch3d K-NN of
  * renderer.py:315,564,627.  verts_s = (verts - Th) @ R when R/Th are non-null (renderer.py:313-314).
  *   grid_hdr[12] x 32 bit: origin xyz, cell, 1/cell (f32), nx, ny, nz, sub (int32 bit patterns), 3 unused;
- *   cell >= cell_size, enlarged only if an axis would exceed 64 cells; scratch: int32[5*n].
- *   cell_start[SHERF_MAX_CELLS+1] int32, cell_pts[n] float4 (x,y,z,bitcast(id)) sorted by cell. */
+ *   cell >= cell_size, enlarged only if an axis would exceed 64 cells; every point's cell index (int)floorf((p - origin) * (1/cell)) is >= 1
+ *   and <= n{x,y,z} - 1 (one whole cell of margin below the lowest point in that very arithmetic); scratch: int32[5*n].
+ *   cell_start[SHERF_MAX_CELLS+1] int32, cell_pts[n] float4 (x,y,z,bitcast(id)) sorted by cell.
+ *   1 <= n <= 65535.  cell_size > 0; with a near_mask (a list for sherf_sample_mask_nn, whose searches reach one cell around a sample) cell_size >=
+ *   SHERF_SHELL_RADIUS, else SHERF_EINVAL.  A list built without a mask on finer cells serves the T-vertex search of sherf_warp_geom only. */
 int sherf_build_cells(const float* verts, int n, const float* R, const float* Th, float cell_size,
                       float* grid_hdr, int32_t* cell_start, float* cell_pts, int32_t* scratch,
                       uint32_t* near_mask, sherf_stream_t stream);
 /* Both per-frame lists in one launch: set 0 = verts_a in the SMPL frame (with near_mask; nullable, see sherf_build_near_lists), set 1 = verts_b untransformed.
- * grid_hdr[2][12], cell_start[2][SHERF_MAX_CELLS+1], cell_pts[2][n][4], scratch[2][5n]. */
+ * grid_hdr[2][12], cell_start[2][SHERF_MAX_CELLS+1], cell_pts[2][n][4], scratch[2][5n].  cell_size >= SHERF_SHELL_RADIUS (set 0 is the sampler's), else SHERF_EINVAL. */
 int sherf_build_cells2(const float* verts_a, const float* R_a, const float* Th_a, const float* verts_b, int n,
                        float cell_size, float* grid_hdr, int32_t* cell_start, float* cell_pts, int32_t* scratch,
                        uint32_t* near_mask, sherf_stream_t stream);
@@ -90,7 +94,7 @@ int sherf_build_cells2(const float* verts_a, const float* R_a, const float* Th_a
  * set of vertices that can lie within `radius` of a point of the sub-cell (the near mask's criterion: box distance < radius + margin),
  * as u16 indices into cell_pts.  near_hdr: int32[2 * SHERF_NEAR_SUBCELLS + 2] = (start, count) per sub-cell + the allocation cursor
  * (zeroed here); near_list: u16[list_cap], list_cap >= 125 n + 3 * SHERF_NEAR_SUBCELLS (every list padded to four entries); the order
- * of a list's entries is unspecified.  Replaces the per-candidate cell walk of pytorch3d's role (renderer.py:313-318) in
+ * of a list's entries is unspecified.  radius >= SHERF_SHELL_RADIUS (else SHERF_EINVAL) and <= the cell list's cell_size.  Replaces the per-candidate cell walk of pytorch3d's role (renderer.py:313-318) in
  * sherf_sample_mask_nn: 40 instead of 75 distance tests per candidate on a body, no segment bookkeeping. */
 #define SHERF_NEAR_SUBCELLS 524288
 int sherf_build_near_lists(const float* grid_hdr, const float* cell_pts, int n, float radius, int32_t* near_hdr,
@@ -111,7 +115,8 @@ int sherf_build_near_lists(const float* grid_hdr, const float* cell_pts, int n, 
  *        count / scan / write so it is deterministic and needs no global atomics.
  *   workspace: dense_vid[R*S] int32, ray_mask[R*ceil(S/64)] u64, scan_ws[R + R/1024 + 2] int32 (the last word is the two-pass sampler's
  *   candidate count).  cs_xs doubles as the sampler's candidate list (capacity records of 16 bytes: x_s + dense index; taken when capacity >= R * S) before the compaction writes it:
- *   its contents on entry are lost.  S <= 256. */
+ *   its contents on entry are lost.  2 <= S <= 256, R * S < 2^31.  The cell list must be one built with cell_size >= SHERF_SHELL_RADIUS (the builders refuse a
+ *   near mask / near lists on finer cells): the shell is 5 cm whatever the grid. */
 /* near_hdr / near_list (both NULL or both set): the near lists of sherf_build_near_lists for the SAME cell list; the two-pass sampler's
  * search then tests one exact list per candidate instead of walking its cell neighbourhood (same results: the comparisons are the same). */
 int sherf_sample_mask_nn(const float* ray_o, const float* ray_d, const float* near, const float* far,

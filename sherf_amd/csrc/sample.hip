@@ -11,6 +11,10 @@
 namespace {
 
 constexpr float kThresh2 = (float)(0.05 * 0.05);   // renderer.py:318 (python float -> fp32 on comparison)
+// The sampler's shell is 5 cm whatever the grid: its searches look at the 3 x 3 x 3 cells around a sample (the near lists: at the sub-cells within one cell of a
+// vertex), which holds every vertex of the shell only on cells of at least that edge.  A finer grid gave a fraction of the valid samples without a word (0.02: 815 of
+// 1873 on tests/test_hipcpu_sampler_edges.py's `body`), so the builders of the sampler's inputs refuse one (SHERF_SHELL_RADIUS in include/sherf_hip.h).
+constexpr float kShellRadius = SHERF_SHELL_RADIUS;
 
 // (v - Th) @ R, evaluated without contraction in the order ((a0*R0c + a1*R1c) + a2*R2c)
 __device__ __forceinline__ void to_smpl_frame(float x, float y, float z, const float* __restrict__ R,
@@ -69,7 +73,17 @@ __device__ __forceinline__ void build_cells_body(const float* __restrict__ verts
         float inv = 1.0f / cell;
         int dims[3];
         for (int c = 0; c < 3; ++c) dims[c] = min(64, (int)floorf((hi[c] - lo[c]) * inv) + 3);
-        s_hdr[0] = lo[0] - cell; s_hdr[1] = lo[1] - cell; s_hdr[2] = lo[2] - cell; s_hdr[3] = cell; s_hdr[4] = inv;
+        // origin = lo - cell, held to "the lowest point's index is >= 1" in the arithmetic every kernel indexes cells with: both subtractions round, so
+        // (lo - origin) * inv can come out an ulp below 1 and the lowest point land in layer 0, against what the header promises (include/sherf_hip.h).
+        // No search was wrong for it (a sample below fl(lo - cell) is at least `cell` away from every point, and layer 0 is searched like any other);
+        // the margin is restored so that nothing built on the promise has to re-derive that.
+        for (int c = 0; c < 3; ++c) {
+            float o = lo[c] - cell;
+            const float step = fmaxf(fabsf(lo[c]), cell) * 2.4e-7f;          // (at least one ulp of o)
+            for (int it = 0; it < 8 && (lo[c] - o) * inv < 1.0f; ++it) o -= step;
+            s_hdr[c] = o;
+        }
+        s_hdr[3] = cell; s_hdr[4] = inv;
         s_hdr[5] = __int_as_float(dims[0]); s_hdr[6] = __int_as_float(dims[1]); s_hdr[7] = __int_as_float(dims[2]);
         const int sub = (8 * dims[0] * dims[1] * dims[2] <= 16384 * 32) ? 2 : 1;   // refined mask must fit 64 KiB of LDS
         s_hdr[8] = __int_as_float(sub); s_hdr[9] = s_hdr[10] = s_hdr[11] = 0.f;
@@ -1102,6 +1116,7 @@ extern "C" int sherf_build_cells(const float* verts, int n, const float* R, cons
     SHERF_CHECK_ARG(verts && grid_hdr && cell_start && cell_pts && scratch);
     SHERF_CHECK_ARG(n > 0 && n <= 65535 && cell_size > 0.f);        // (u16 point indices in the sampler's candidate records)
     SHERF_CHECK_ARG((R == nullptr) == (Th == nullptr));
+    SHERF_CHECK_ARG(near_mask == nullptr || cell_size >= kShellRadius);   // (the near mask serves the sampler: see kShellRadius)
     hipLaunchKernelGGL(build_cells_kernel, dim3(1), dim3(1024), 0, as_stream(stream), verts, n, R, Th, cell_size,
                        grid_hdr, cell_start, reinterpret_cast<float4*>(cell_pts), scratch, near_mask);
     if (near_mask) {
@@ -1116,7 +1131,7 @@ extern "C" int sherf_build_cells2(const float* verts_a, const float* R_a, const 
                                   float cell_size, float* grid_hdr, int32_t* cell_start, float* cell_pts, int32_t* scratch,
                                   uint32_t* near_mask, sherf_stream_t stream) {
     SHERF_CHECK_ARG(verts_a && R_a && Th_a && verts_b && grid_hdr && cell_start && cell_pts && scratch);
-    SHERF_CHECK_ARG(n > 0 && n <= 65535 && cell_size > 0.f);        // (u16 point indices in the sampler's candidate records)
+    SHERF_CHECK_ARG(n > 0 && n <= 65535 && cell_size >= kShellRadius);   // (u16 point indices in the sampler's candidate records; set 0 is the sampler's: see kShellRadius)
     hipLaunchKernelGGL(build_cells2_kernel, dim3(2), dim3(1024), 0, as_stream(stream), verts_a, R_a, Th_a, verts_b, n, cell_size,
                        grid_hdr, cell_start, reinterpret_cast<float4*>(cell_pts), scratch, near_mask);
     if (near_mask) {                                                 // (NULL: sherf_build_near_lists writes the mask from its counts)
@@ -1130,7 +1145,7 @@ extern "C" int sherf_build_cells2(const float* verts_a, const float* R_a, const 
 extern "C" int sherf_build_near_lists(const float* grid_hdr, const float* cell_pts, int n, float radius, int32_t* near_hdr,
                                       uint16_t* near_list, int64_t list_cap, uint32_t* near_mask, sherf_stream_t stream) {
     SHERF_CHECK_ARG(grid_hdr && cell_pts && near_hdr && near_list);
-    SHERF_CHECK_ARG(n > 0 && n <= 65535 && radius > 0.f && list_cap >= (int64_t)125 * n + 3 * SHERF_NEAR_SUBCELLS);
+    SHERF_CHECK_ARG(n > 0 && n <= 65535 && radius >= kShellRadius && list_cap >= (int64_t)125 * n + 3 * SHERF_NEAR_SUBCELLS);   // (a list must hold every vertex of the sampler's shell)
     hipStream_t st = as_stream(stream);
     int2* nh = reinterpret_cast<int2*>(near_hdr);
     int32_t* cursor = near_hdr + 2 * SHERF_NEAR_SUBCELLS;                 // the word behind the last header
