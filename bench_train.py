@@ -8,6 +8,8 @@ The backward pipeline (sherf_amd/backward.py) is checked ag
 tests/test_gpu_backward.py (`pytest -m gpu`).  Rank 0 prints ONE JSON line; `roofline` is the step's dominant kernel
 (sherf_gather_tokens_bwd: the scatter of d_tokens into the tri-planes, the feature map and the voxel rows with fp32 atomics), timed
 with events on the launch stream inside the timed steps; `phases_ms` splits a step into forward / backward / all-reduce + Adam.
+`--branches abc` (default 111): the renderer's use_1d / use_2d / use_3d_feature switches, e.g. 110 trains without the voxel branch (the scatter
+then runs through sherf_gather_tokens_bwd_masked).
 """
 import argparse
 import json
@@ -31,7 +33,11 @@ def main():
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)       # two steps under rocprofv3 --pmc: nothing printed
     ap.add_argument('--no-pmc', action='store_true', help='skip the two rocprofv3 --pmc passes that count the tap scatter\'s HBM bytes')
     ap.add_argument('--osg', action='store_true', help='the generator of the reference\'s constructor defaults: use_NeRF_decoder=False, OSGDecoder (same JSON keys)')
+    ap.add_argument('--branches', default='111', help='use_1d_feature / use_2d_feature / use_3d_feature as three digits, e.g. 110 = no voxel branch (default 111: all three)')
     a = ap.parse_args()
+    if len(a.branches) != 3 or set(a.branches) - set('01'):
+        ap.error('--branches takes three digits 0 / 1, e.g. 110')
+    branches = tuple(ch == '1' for ch in a.branches)
     if a.pmc_child:
         a.steps, a.warmup = 2, 1
     import bench
@@ -68,7 +74,7 @@ def main():
     from sherf_amd.voxel import SparseConvTensor
     smpl = synth.make_synth_smpl(0)
     fx, d, to = bench.make_inputs(a.config, 0.4 + rank * 2 * np.pi / max(world, 1), dev)
-    rend = ImportanceRenderer(True, True, True, use_trans=True, use_NeRF_decoder=not a.osg, smpl=smpl)
+    rend = ImportanceRenderer(*branches, use_trans=True, use_NeRF_decoder=not a.osg, smpl=smpl)
     variant = fixtures.variant_of(a.config)                  # ('_ri' configurations: the reference-init network, as in bench.py)
     fixtures.load_seeded_state(rend, 'renderer.', variant)
     if a.osg:
@@ -127,7 +133,7 @@ def main():
     scatter_ev, call0 = [], _lib.call
 
     def timed_call(name, *args):
-        if name != 'sherf_gather_tokens_bwd_binned':
+        if name not in ('sherf_gather_tokens_bwd_binned', 'sherf_gather_tokens_bwd_masked'):      # (masked: a step with a feature branch off)
             return call0(name, *args)
         e0, e1 = _Ev(), _Ev()
         e0.record(); call0(name, *args); e1.record()
@@ -195,7 +201,7 @@ def main():
             traffic = None
             under_profiler = any(k.startswith(('ROCPROF', 'ROCP_TOOL')) for k in os.environ)      # (never a counter pass inside somebody else's rocprofv3 run)
             if world == 1 and not a.no_pmc and not under_profiler:
-                t = bench.pmc_traffic(a, lrank, timeout=240, child=[sys.executable, os.path.abspath(__file__), '--pmc-child', '--config', a.config] + (['--osg'] if a.osg else []),
+                t = bench.pmc_traffic(a, lrank, timeout=240, child=[sys.executable, os.path.abspath(__file__), '--pmc-child', '--config', a.config, '--branches', a.branches] + (['--osg'] if a.osg else []),
                                       keys=('gather_tokens_bwd_runs_kernel',))
                 traffic = t.get('hbm_bytes_per_launch') if isinstance(t, dict) and 'error' not in t else t
             roofline = dict(kernel='gather_tokens_bwd_runs_kernel (the tap scatter of sherf_gather_tokens_bwd_binned; events also cover its bin count / scans / fill)', bound='hbm',
@@ -210,7 +216,7 @@ def main():
                               scaling='weak', vs_baseline=None, dtype='f32 (backward: fp32 kernels, MFMA GEMMs on a three-part bf16 split, MFMA sparse-conv input gradient on a range-scaled fp16 split; forward: f16x3 MFMA)',
                               data='synthetic', final_loss=float(loss), phases_ms=phases,
                               host_ms=dict(zip(('forward', 'backward', 'allreduce_adam'), (1e3 * np.mean(host_t, 0)).tolist())), roofline=roofline,
-                              dist=dist_info, config=dict(workload=f'{a.config}{" (OSGDecoder)" if a.osg else ""}: one view per GPU, stub loss MSE(rgb)+MSE(acc)', rays=R))))
+                              dist=dist_info, config=dict(workload=f'{a.config}{" (OSGDecoder)" if a.osg else ""}{"" if all(branches) else " (feature branches " + a.branches + ")"}: one view per GPU, stub loss MSE(rgb)+MSE(acc)', rays=R))))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

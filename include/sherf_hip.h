@@ -185,6 +185,17 @@ int sherf_gather_tokens_bwd_binned(const int32_t* counters, const float* geom, c
                                    float* d_rows0, float* d_rows1, float* d_rows2, float* d_tok_bias, int32_t* scratch,
                                    int64_t scratch_words, sherf_stream_t stream);
 int sherf_gather_bwd_scratch_words(const sherf_vox_level* levels_host, int64_t capacity, int64_t* words_host);
+/* The scatter for a renderer with feature branches switched off (use_1d / use_2d / use_3d_feature): sherf_gather_tokens_bwd_binned's contract plus
+ * `branches`, bit 0 (1) = tri-plane taps, bit 1 (2) = pixel-aligned taps, bit 2 (4) = voxel taps; anything outside 1..7 is SHERF_EINVAL, nothing is
+ * launched.  An absent branch costs nothing in the kernel (no stencil, no running sums, no atomics: one instance per mask), and its outputs
+ * (d_planes_f; d_feat_f; d_rows0..2) may be NULL -- they are never read or written.  levels_host stays required whatever the mask: the samples are
+ * walked in the order of their finest voxel cell, which is what keeps the plane and pixel texels the same over runs of samples.  d_tok_bias is always
+ * summed.  Always the run-length form (csrc/gather.hip: gather_tokens_bwd_runs_kernel); branches == 7 launches the very kernel of the entry above. */
+int sherf_gather_tokens_bwd_masked(const int32_t* counters, const float* geom, const float* d_tokens, int P, int Hf, int Wf,
+                                   int H, int W, const sherf_vox_level* levels_host, const float* bounds, const float* vox_min,
+                                   const int32_t* vox_sh_host, int64_t capacity, float* d_planes_f, float* d_feat_f,
+                                   float* d_rows0, float* d_rows1, float* d_rows2, float* d_tok_bias, int32_t* scratch,
+                                   int64_t scratch_words, int branches, sherf_stream_t stream);
 
 int sherf_fold_tables(const float* in, const float* Wt, float* out, int HW, int groups, int pix_stride,
                       int64_t group_base, int out_half, sherf_stream_t stream);

@@ -92,6 +92,15 @@ def composite_bits(white_back, clamp_mode='relu'):
     return (COMPOSITE_WHITE_BACK if white_back else 0) | (COMPOSITE_SOFTPLUS if clamp_mode == 'softplus' else 0)
 
 
+# the `branches` argument of sherf_gather_tokens_bwd_masked (include/sherf_hip.h)
+BRANCH_PLANES, BRANCH_PIXEL, BRANCH_VOXEL = 1, 2, 4
+
+
+def branch_mask(on):
+    """ImportanceRenderer.feature_branches() -> (1d, 2d, 3d) as the scatter's `branches` bits."""
+    return (BRANCH_PLANES if on[0] else 0) | (BRANCH_PIXEL if on[1] else 0) | (BRANCH_VOXEL if on[2] else 0)
+
+
 # bits of sherf_frame.mlp_prec beside the precision (include/sherf_hip.h: SHERF_MLP_*)
 MLP_NO_TRANSFORMER, MLP_OSG_DECODER = 256, 512
 

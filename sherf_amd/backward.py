@@ -48,7 +48,10 @@ def composite_backward(renderer, d_rgb, d_acc, ray_directions, near, far, white_
 
 def render_backward(renderer, decoder, d_rgb, d_acc):
     """Full backward of the last `renderer.forward(...)` (training mode).  d_rgb [1,R,3], d_acc [1,R,1].
-    -> dict(params={reference name: grad}, planes [1,3,32,P,P], obs_feat [1,64,Hf,Wf], vertex_feat [N,32])."""
+    -> dict(params={reference name: grad}, planes [1,3,32,P,P], obs_feat [1,64,Hf,Wf], vertex_feat [N,32]).
+    A renderer with a feature branch switched off (renderer.feature_branches()): the dense stage and the tap backward read the EFFECTIVE reprojection
+    matrix, the scatter leaves the absent branches' taps out (sherf_gather_tokens_bwd_masked), the sparse encoder's backward runs only with the voxel
+    branch; `params` holds the parameters the reference's autograd reaches, and an absent branch's input gradient is None."""
     last = renderer.last
     if last is None or 'bwd' not in last:
         raise RuntimeError('render_backward needs a preceding forward call')
@@ -57,6 +60,12 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
     f32 = lambda t: t.detach().to(dtype=torch.float32).contiguous()
     state = {'renderer.' + k: v for k, v in renderer.state_dict().items()}
     state.update({'decoder.' + k: v for k, v in decoder.state_dict().items()})
+    on = renderer.feature_branches()
+    if sum(on) != 3:
+        # the forward's effective [32, 96] matrix + bias under the module's names (as _pack_stream / _pack_osg read it): the slot-2 completion and the
+        # tap backward see a zero block for an absent branch, the identity for the tri-planes alone
+        Wr, br = renderer._effective_reprojection()
+        state['renderer.conv1d_reprojection.weight'], state['renderer.conv1d_reprojection.bias'] = Wr[:, :, None], br
     ops = HipOps()
     # ---- a16 ----
     d_sample = composite_backward(renderer, d_rgb, d_acc, b['ray_d'], b['near'], b['far'], b['white_back'], b.get('clamp_mode', 'relu')).contiguous()
@@ -87,14 +96,24 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
         words = ctypes.c_int64(0)
         _lib.call('sherf_gather_bwd_scratch_words', last['levels_struct'], last['cap'], ctypes.byref(words))
         scratch = torch.empty(words.value, dtype=torch.int32, device=dev)
-        _lib.call('sherf_gather_tokens_bwd_binned', _lib.ptr(ws['counters']), _lib.ptr(ws['geom']), _lib.ptr(d_tiled), P_, Hf, Wf, b['H'], b['W'],
-                  last['levels_struct'], _lib.ptr(bounds), _lib.ptr(vox_min), vox_sh, last['cap'], ops._p(d_planes_f), ops._p(d_feat_f),
-                  ops._p(d_rows[0]), ops._p(d_rows[1]), ops._p(d_rows[2]), ops._p(d_bias), _lib.ptr(scratch), words.value, _lib.stream())
+        p = lambda m: None if m is None else ops._p(m)                 # (an absent branch has no table: NULL, never dereferenced)
+        d_rows = d_rows or (None, None, None)
+        args = (_lib.ptr(ws['counters']), _lib.ptr(ws['geom']), _lib.ptr(d_tiled), P_, Hf, Wf, b['H'], b['W'],
+                last['levels_struct'], _lib.ptr(bounds), _lib.ptr(vox_min), vox_sh, last['cap'], p(d_planes_f), p(d_feat_f),
+                p(d_rows[0]), p(d_rows[1]), p(d_rows[2]), ops._p(d_bias), _lib.ptr(scratch), words.value)
+        if sum(on) == 3:
+            _lib.call('sherf_gather_tokens_bwd_binned', *args, _lib.stream())
+        else:                                                          # the taps of the absent branches left out of the kernel
+            _lib.call('sherf_gather_tokens_bwd_masked', *args, _lib.branch_mask(on), _lib.stream())
 
     ctx = dict(n=n, P=P_, Hf=Hf, Wf=Wf, planes=Mat(planes.view(-1), 96, P_ * P_), obs_feat=Mat(obs_feat.view(-1), 64, Hf * Wf),
                levels=levels_ctx, scatter=scatter)
-    taps = taps_backward(ops, state, ctx, d_tin, dWb_pe)
+    taps = taps_backward(ops, state, ctx, d_tin, dWb_pe, on)
     grads.update(taps['grads'])
+    grad_in = lambda m, *shape: None if m is None else m.tensor().view(*shape).clone()
+    d_planes, d_obs = grad_in(taps['d_planes'], 1, 3, 32, P_, P_), grad_in(taps['d_obs_feat'], 1, 64, Hf, Wf)
+    if not on[2]:                                                           # no voxel taps: nothing reaches the sparse encoder (renderer.py:345-352)
+        return dict(params=grads, planes=d_planes, obs_feat=d_obs, vertex_feat=None)
     # ---- a11 ----
     lev_ctx = [dict(keys=L[i]['keys'], wp=L[i]['wp'], n_rows=L[i]['n_rows'], dims=tuple(shapes[i]), cap=L[i]['cap']) for i in range(4)]
     layers = [dict(wname='renderer.encoder_3d.' + m['wname'], bname='renderer.encoder_3d.' + m['bname'], cin=m['cin'], cout=m['cout'],
@@ -105,8 +124,7 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
     ectx = dict(levels=lev_ctx, mult=L[0]['mult'], n_total=L[0]['n_total'], coord=b['coord'], N=N, g0=Mat.of(L[0]['g0']), layers=layers)
     d_feat, g_enc = encoder_backward(ops, state, ectx, taps['d_levels'])
     grads.update(g_enc)
-    return dict(params=grads, planes=taps['d_planes'].tensor().view(1, 3, 32, P_, P_).clone(),
-                obs_feat=taps['d_obs_feat'].tensor().view(1, 64, Hf, Wf).clone(), vertex_feat=d_feat.tensor().clone())
+    return dict(params=grads, planes=d_planes, obs_feat=d_obs, vertex_feat=d_feat.tensor().clone())
 
 
 class RenderFunction(torch.autograd.Function):

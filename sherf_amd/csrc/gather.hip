@@ -1126,12 +1126,17 @@ __global__ void __launch_bounds__(256) bin_fill_blocks_kernel(const int32_t* __r
     w.sorted[w.blocks[b >> 10] + w.offsets[b] + atomicAdd(w.cursor + b, 1)] = (int32_t)c;
 }
 
+// BR: the feature branches whose taps are scattered (sherf_gather_tokens_bwd_masked) -- bit 0 the tri-planes, bit 1 the pixel-aligned feature map, bit 2 the
+// voxel rows.  An absent branch has no stencil, no running sums and no atomics in its instance (compile-time: the registers of the sums are the kernel's
+// budget), and its output pointers are never read; the walk, the sorted order and d_tok_bias are those of the all-on instance <7>, whose code is unchanged.
+template <int BR>
 __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const int32_t* __restrict__ counters, int64_t capacity, const float* __restrict__ geom,
                                                                         const float4* __restrict__ d_tokens, int P, int Hf, int Wf, int H, int W, LevelsBwd lv,
                                                                         const float* __restrict__ bounds, const float* __restrict__ vox_min, int3 vox_sh,
                                                                         const int32_t* __restrict__ sorted, float4* __restrict__ d_planes_f,
                                                                         float4* __restrict__ d_feat_f, float* __restrict__ d_tok_bias, int dbg) {
-    const bool do_pix = !(dbg & 16384), do_vox = !(dbg & 32768), do_pl = !(dbg & 65536);          // (timing ablations as above)
+    constexpr bool kPl = (BR & 1) != 0, kPix = (BR & 2) != 0, kVox = (BR & 4) != 0;
+    const bool do_pix = kPix && !(dbg & 16384), do_vox = kVox && !(dbg & 32768), do_pl = kPl && !(dbg & 65536);          // (timing ablations as above)
     __shared__ float s_bias[96];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, c31 = lane & 31;
     const sherf_vox_level levs[3] = {lv.l[0], lv.l[1], lv.l[2]};
@@ -1208,6 +1213,7 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
             float n[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) n[a] = 2.f * (gm[a] - bounds[a]) / (bounds[3 + a] - bounds[a]) - 1.f;
+            if constexpr (kPl) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const PlaneTap t = plane_tap(p, n, P);
@@ -1219,6 +1225,8 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
                     wpl[4 * p + k] = (live && do_pl) ? ((k & 1) ? t.fx : 1.f - t.fx) * ((k >> 1) ? t.fy : 1.f - t.fy) : 0.f;
                 }
             }
+            }
+            if constexpr (kPix) {
             const PixTap t = pix_tap(gm, W, H, Wf, Hf);
             kf = (t.yi + 2) * (Wf + 4) + (t.xi + 2);
 #pragma unroll
@@ -1227,6 +1235,8 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
                 tf[k] = (live && do_pix && xx >= 0 && xx < Wf && yy >= 0 && yy < Hf) ? yy * Wf + xx : -1;
                 wfm[k] = (live && do_pix) ? ((k & 1) ? t.fx : 1.f - t.fx) * ((k >> 1) ? t.fy : 1.f - t.fy) : 0.f;
             }
+            }
+            if constexpr (kVox) {
             float gx, gy, gz;
             vox_grid_coords(gm, vox_min, vox_sh, gx, gy, gz);
 #pragma unroll
@@ -1246,6 +1256,7 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
                     tv[8 * L + k] = (in && (rr.x & bit)) ? (int)(rr.y + __popc(rr.x & (bit - 1u))) : -1;
                 }
             }
+            }
         }
         // ---- (2) lane = channel ----
         const int nact = (int)min((int64_t)64, nv - base);
@@ -1260,6 +1271,7 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
             bs0 += d0; bs1 += half ? 0.f : d1;
 #define SHERF_RL(v) __builtin_amdgcn_readlane((v), sidx)
 #define SHERF_RLF(v) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), sidx))
+            if constexpr (kPl) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const float dpv = p == 0 ? dp0 : (p == 1 ? dp1 : d1);
@@ -1279,7 +1291,8 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
                     accp[p][dy] += (half ? wB : wA) * dpv;
                 }
             }
-            {
+            }
+            if constexpr (kPix) {
                 const int key = SHERF_RL(kf);
                 if (key != curf) {
                     if (curf >= 0) flush_feat();
@@ -1293,6 +1306,7 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
 #pragma unroll
                 for (int k = 0; k < 4; ++k) accf[k] += SHERF_RLF(wfm[k]) * d0;
             }
+            if constexpr (kVox) {
 #pragma unroll
             for (int L = 0; L < 3; ++L) {
                 const int cell = SHERF_RL(ck[L]);
@@ -1313,18 +1327,25 @@ __global__ void __launch_bounds__(kBinNT) gather_tokens_bwd_runs_kernel(const in
                     accb[L][k] += (half ? wB : wA) * d1;
                 }
             }
+            }
 #undef SHERF_RL
 #undef SHERF_RLF
           }
         }
     }
+    if constexpr (kVox) {
 #pragma unroll
     for (int L = 0; L < 3; ++L)
         if (cur[L] >= 0) flush(L);
+    }
+    if constexpr (kPl) {
 #pragma unroll
     for (int p = 0; p < 3; ++p)
         if (curp[p] >= 0) flush_plane(p);
+    }
+    if constexpr (kPix) {
     if (curf >= 0) flush_feat();
+    }
     // d_tok_bias
     for (int i = tid; i < 96; i += kBinNT) s_bias[i] = 0.f;
     __syncthreads();
@@ -1463,6 +1484,35 @@ extern "C" int sherf_gather_bwd_scratch_words(const sherf_vox_level* levels_host
     return SHERF_OK;
 }
 
+// The "runs" form of the scatter (gather_tokens_bwd_runs_kernel<branches>): sort by the finest tapped cell, then the walk.  Arguments checked by the callers.
+static int gather_tokens_bwd_runs(const int32_t* counters, const float* geom, const float* d_tokens, int P, int Hf, int Wf, int H, int W, const LevelsBwd& lv,
+                                  const float* bounds, const float* vox_min, int3 sh, int64_t capacity, float* d_planes_f, float* d_feat_f,
+                                  float* d_tok_bias, int32_t* scratch, int branches, hipStream_t st) {
+    SHERF_CHECK_ARG((int64_t)(lv.l[0].D + 4) * (lv.l[0].H + 4) * (lv.l[0].W + 4) < (int64_t)1 << 30);
+    const int nb = bwd_bins(lv.l[0]), n_blocks = (nb + 1023) / 1024;
+    const BinWs w0 = bin_ws(scratch, nb, capacity);
+    SHERF_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(4 + 2 * (int64_t)nb) * sizeof(int32_t), st));
+    const unsigned sb0 = (unsigned)((capacity + 255) / 256);
+    hipLaunchKernelGGL(bin_count_kernel, dim3(sb0), dim3(256), 0, st, counters, geom, lv.l[0], vox_min, sh, capacity, w0);
+    hipLaunchKernelGGL(bin_scan_blocks_kernel, dim3(n_blocks), dim3(1024), 0, st, w0);
+    hipLaunchKernelGGL(bin_scan_top_kernel, dim3(1), dim3(1024), 0, st, w0, n_blocks);
+    hipLaunchKernelGGL(bin_fill_blocks_kernel, dim3(sb0), dim3(256), 0, st, counters, capacity, w0);
+    const int64_t chunks = (capacity + 63) / 64;
+    const int grid = (int)(chunks / 4 + 1 < 4 * n_cus() ? chunks / 4 + 1 : 4 * n_cus());
+#define SHERF_RUNS(BR)                                                                                                                                  \
+    case BR:                                                                                                                                            \
+        hipLaunchKernelGGL(gather_tokens_bwd_runs_kernel<BR>, dim3(grid), dim3(kBinNT), 0, st, counters, capacity, geom,                                  \
+                           reinterpret_cast<const float4*>(d_tokens), P, Hf, Wf, H, W, lv, bounds, vox_min, sh, w0.sorted,                                \
+                           reinterpret_cast<float4*>(d_planes_f), reinterpret_cast<float4*>(d_feat_f), d_tok_bias, g_sherf_debug);                        \
+        break
+    switch (branches) {
+        SHERF_RUNS(1); SHERF_RUNS(2); SHERF_RUNS(3); SHERF_RUNS(4); SHERF_RUNS(5); SHERF_RUNS(6); SHERF_RUNS(7);
+        default: SHERF_CHECK_ARG(false);
+    }
+#undef SHERF_RUNS
+    SHERF_LAUNCH_CHECK();
+}
+
 extern "C" int sherf_gather_tokens_bwd_binned(const int32_t* counters, const float* geom, const float* d_tokens, int P, int Hf, int Wf,
                                               int H, int W, const sherf_vox_level* levels_host, const float* bounds, const float* vox_min,
                                               const int32_t* vox_sh_host, int64_t capacity, float* d_planes_f, float* d_feat_f,
@@ -1480,23 +1530,8 @@ extern "C" int sherf_gather_tokens_bwd_binned(const int32_t* counters, const flo
     lv.d_rows[0] = d_rows0; lv.d_rows[1] = d_rows1; lv.d_rows[2] = d_rows2;
     const int3 sh = make_int3(vox_sh_host[0], vox_sh_host[1], vox_sh_host[2]);
     hipStream_t st = as_stream(stream);
-    if (!(sherf_experiment() & 256)) {               // round 5: samples in the order of their finest cell, every level's sums in registers (SHERF_EXPERIMENT bit 8: round 3's kernel)
-        SHERF_CHECK_ARG((int64_t)(lv.l[0].D + 4) * (lv.l[0].H + 4) * (lv.l[0].W + 4) < (int64_t)1 << 30);
-        const int nb = bwd_bins(lv.l[0]), n_blocks = (nb + 1023) / 1024;
-        const BinWs w0 = bin_ws(scratch, nb, capacity);
-        SHERF_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(4 + 2 * (int64_t)nb) * sizeof(int32_t), st));
-        const unsigned sb0 = (unsigned)((capacity + 255) / 256);
-        hipLaunchKernelGGL(bin_count_kernel, dim3(sb0), dim3(256), 0, st, counters, geom, lv.l[0], vox_min, sh, capacity, w0);
-        hipLaunchKernelGGL(bin_scan_blocks_kernel, dim3(n_blocks), dim3(1024), 0, st, w0);
-        hipLaunchKernelGGL(bin_scan_top_kernel, dim3(1), dim3(1024), 0, st, w0, n_blocks);
-        hipLaunchKernelGGL(bin_fill_blocks_kernel, dim3(sb0), dim3(256), 0, st, counters, capacity, w0);
-        const int64_t chunks = (capacity + 63) / 64;
-        const int grid = (int)(chunks / 4 + 1 < 4 * n_cus() ? chunks / 4 + 1 : 4 * n_cus());
-        hipLaunchKernelGGL(gather_tokens_bwd_runs_kernel, dim3(grid), dim3(kBinNT), 0, st, counters, capacity, geom, reinterpret_cast<const float4*>(d_tokens),
-                           P, Hf, Wf, H, W, lv, bounds, vox_min, sh, w0.sorted, reinterpret_cast<float4*>(d_planes_f), reinterpret_cast<float4*>(d_feat_f),
-                           d_tok_bias, g_sherf_debug);
-        SHERF_LAUNCH_CHECK();
-    }
+    if (!(sherf_experiment() & 256))                 // round 5: samples in the order of their finest cell, every level's sums in registers (SHERF_EXPERIMENT bit 8: round 3's kernel)
+        return gather_tokens_bwd_runs(counters, geom, d_tokens, P, Hf, Wf, H, W, lv, bounds, vox_min, sh, capacity, d_planes_f, d_feat_f, d_tok_bias, scratch, 7, st);
     const int n_bins = bwd_bins(lv.l[2]);
     const BinWs w = bin_ws(scratch, n_bins, capacity);
     SHERF_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(4 + 2 * (int64_t)n_bins) * sizeof(int32_t), st));      // list length, counts, cursors
@@ -1509,4 +1544,27 @@ extern "C" int sherf_gather_tokens_bwd_binned(const int32_t* counters, const flo
                        reinterpret_cast<const float4*>(d_tokens), P, Hf, Wf, H, W, lv, bounds, vox_min, sh, w,
                        reinterpret_cast<float4*>(d_planes_f), reinterpret_cast<float4*>(d_feat_f), d_tok_bias, g_sherf_debug);
     SHERF_LAUNCH_CHECK();
+}
+
+extern "C" int sherf_gather_tokens_bwd_masked(const int32_t* counters, const float* geom, const float* d_tokens, int P, int Hf, int Wf,
+                                              int H, int W, const sherf_vox_level* levels_host, const float* bounds, const float* vox_min,
+                                              const int32_t* vox_sh_host, int64_t capacity, float* d_planes_f, float* d_feat_f,
+                                              float* d_rows0, float* d_rows1, float* d_rows2, float* d_tok_bias, int32_t* scratch,
+                                              int64_t scratch_words, int branches, sherf_stream_t stream) {
+    SHERF_CHECK_ARG(branches >= 1 && branches <= 7);
+    SHERF_CHECK_ARG(counters && geom && d_tokens && levels_host && bounds && vox_min && vox_sh_host && d_tok_bias && scratch);
+    SHERF_CHECK_ARG(!(branches & 1) || d_planes_f);
+    SHERF_CHECK_ARG(!(branches & 2) || d_feat_f);
+    SHERF_CHECK_ARG(!(branches & 4) || (d_rows0 && d_rows1 && d_rows2));
+    SHERF_CHECK_ARG(P > 0 && Hf > 0 && Wf > 0 && H > 0 && W > 0 && capacity > 0);
+    LevelsBwd lv = {};
+    for (int i = 0; i < 3; ++i) {                  // (the levels stay required with the voxel branch absent: the samples are sorted by their finest cell)
+        lv.l[i] = levels_host[i];
+        SHERF_CHECK_ARG(lv.l[i].wp && lv.l[i].D > 0 && lv.l[i].H > 0 && lv.l[i].W > 0);
+    }
+    SHERF_CHECK_ARG(scratch_words >= bwd_scratch_words(levels_host, capacity));
+    lv.d_rows[0] = d_rows0; lv.d_rows[1] = d_rows1; lv.d_rows[2] = d_rows2;
+    const int3 sh = make_int3(vox_sh_host[0], vox_sh_host[1], vox_sh_host[2]);
+    return gather_tokens_bwd_runs(counters, geom, d_tokens, P, Hf, Wf, H, W, lv, bounds, vox_min, sh, capacity, d_planes_f, d_feat_f, d_tok_bias, scratch,
+                                  branches, as_stream(stream));
 }

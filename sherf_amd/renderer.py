@@ -1031,13 +1031,12 @@ class ImportanceRenderer(nn.Module):
     def forward(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
                 decoder, ray_origins, ray_directions, near, far, input_data, rendering_options):
         if getattr(self, 'enable_autograd', False) and torch.is_grad_enabled() and not getattr(self, '_in_autograd', False):
-            if sum(self.feature_branches()) != 3:
-                raise NotImplementedError('the backward through the HIP kernels covers all three feature branches (use_trans True or False); a renderer with a feature branch switched off is forward-only')
             if not self.use_NeRF_decoder and not getattr(self, 'enable_osg_autograd', False):
                 raise NotImplementedError('the backward of the OSG path (use_NeRF_decoder=False: OSGDecoder, sherf_osg_decoder / sherf_bwd_osg_head) is staged: '
                                           'with enable_autograd alone this renderer is forward-only; set enable_osg_autograd = True beside it to train through it')
             # opt-in training path (BASELINE config 5): the same forward, recorded as one autograd node whose backward runs
-            # the HIP backward pipeline (sherf_amd/backward.py; experimental until verified on hardware)
+            # the HIP backward pipeline (sherf_amd/backward.py; experimental until verified on hardware).  Every combination of the feature-branch
+            # switches trains: the backward leaves the absent branches out (backward.py: render_backward)
             from .backward import RenderFunction, _named_params
 
             def call():
@@ -1267,7 +1266,11 @@ class ImportanceRenderer(nn.Module):
                 and not (fr.flags & 8) and int(fr.mlp_parts) <= 1 and rng is None:
             self._tune_mlp_form(fr, ws, dev, cfg[0], levels, (s_main, s_side, s_aux))    # (the frame above is complete and correct; the forms are timed behind it)
         ws['rgb'], ws['depth'], ws['acc'] = out[:3 * R].view(R, 3), out[3 * R:4 * R], out[4 * R:]
-        self.encoder_3d.finish(pl)                      # (on the encoder's own stream instead: measured, no gain -- DESIGN 9.38)
+        # BatchNorm running statistics.  A grad-recorded forward follows the reference, which runs encoder_3d only under `if self.use_3d_feature`
+        # (renderer.py:345-352): a renderer BUILT with use_3d_feature=False leaves every encoder_3d buffer alone (the constructor's switch, not
+        # feature_branches(): (False, False, True) still runs the encoder there and uses nothing of it).  The plain no-grad forward is as it was.
+        if self.use_3d_feature or not getattr(self, '_in_autograd', False):
+            self.encoder_3d.finish(pl)                  # (on the encoder's own stream instead: measured, no gain -- DESIGN 9.38)
         if decide is not None:
             decide()
         if not (torch.is_grad_enabled() and getattr(self, 'enable_autograd', False)) and not getattr(self, '_in_autograd', False):
