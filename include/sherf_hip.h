@@ -465,6 +465,18 @@ int sherf_svox_encode(const sherf_svox_plan* plan, const int32_t* coord, const f
  * network kernel (sherf_nerf_mlp3_pe) instead of evaluated in it -- the network kernel runs at the board's power cap, the gather waits on memory.  Same
  * operand bits: the frame is bit-identical. */
 #define SHERF_FRAME_PE_FRAGS 128
+/* frame->flags & SHERF_FRAME_REUSE_OBSERVATION (opt-in): the frame renders from the observation state the LAST frame that encoded into the same
+ * buffers left there -- planes_f, feat_f, img4 and the three voxel levels -- instead of rebuilding it: phase 1 enqueues neither the table folds
+ * (sherf_fold_tables x2, sherf_img_to_hwc4) nor the sparse voxel encoder (~50 launches).  `levels_out_host` is then an INPUT: the array the
+ * encoding frame's call filled in (a pure function of the plan: rows == vox_plan->fold_rows; anything else is SHERF_EINVAL).  The per-frame SMPL
+ * tables, which otherwise ride inside the encoder's enqueue, are enqueued by the driver itself, on stream_aux when there is one, else on
+ * stream_side.  Every stream that works in the frame still waits for the frame's start event; the frame waits for no event it did not record
+ * itself (no encoder / fold / level event; main_after_layer is ignored) -- its order behind the encoding frame is the caller's stream alone: that
+ * frame's gather waited for its encoder and folds, and this frame's gather is enqueued behind it on stream_main.  So the caller must issue the
+ * reusing frame on the stream the encoding frame was issued on, with nothing in between that rewrites those buffers; whether the buffers still
+ * hold THIS observation under THESE weights and precisions is the caller's to know (sherf_amd.ImportanceRenderer keys it).  Same bits as the
+ * frame that encodes.  Phases 2 and 4, the count reports, the OSG decoder and every launch form of the network are unchanged under the flag. */
+#define SHERF_FRAME_REUSE_OBSERVATION 256
 typedef struct {
     /* SMPL (a7-a9) */
     const float* poses; const float* shapes;           /* [3][72], [3][10]: target, big-pose, observation */
@@ -524,6 +536,9 @@ int sherf_frame_count(int32_t* nv_host);
  * enqueued frames, failed captures} since load. */
 int sherf_frame_graphs(int enable);
 int sherf_frame_graph_stats(int64_t* stats_host, int32_t n);
+/* {frames whose phase 1 encoded the observation, frames whose phase 1 reused it (SHERF_FRAME_REUSE_OBSERVATION)} since load, replayed graphs
+ * included; n >= 2.  Callers read deltas. */
+int sherf_frame_observation_stats(int64_t* stats_host, int32_t n);
 /* phase: 1 = everything up to the per-sample network, 2 = compositing, 3 = both; 4 (alone) = the sampler only (cell lists, shell mask,
  * nearest vertex, compaction: counters[0] = the frame's number of valid samples) -- what a caller runs once to size tok_capacity. */
 /* stream_aux (may be NULL): a third stream on which the occupancy structure of voxel levels 1-3 is built while the

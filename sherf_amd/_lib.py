@@ -105,6 +105,17 @@ def branch_mask(on):
 MLP_NO_TRANSFORMER, MLP_OSG_DECODER = 256, 512
 
 
+# sherf_frame.flags: render from the observation state the last encoding frame left in the same buffers (include/sherf_hip.h)
+FRAME_REUSE_OBSERVATION = 256
+
+
+def frame_observation_stats():
+    """sherf_frame_observation_stats: (frames that encoded the observation, frames that reused it) since the library was loaded."""
+    s = (ctypes.c_int64 * 2)()
+    call('sherf_frame_observation_stats', s, 2)
+    return int(s[0]), int(s[1])
+
+
 _SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
             'sherf_stream_t': ctypes.c_void_p}
 

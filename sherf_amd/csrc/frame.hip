@@ -186,6 +186,10 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         SHERF_HIP_CHECK(hipEventRecord(d.ev_start, main));
         SHERF_CAP_TRACE("side waits ev_start");
         SHERF_HIP_CHECK(hipStreamWaitEvent(side, d.ev_start, 0));
+        // SHERF_FRAME_REUSE_OBSERVATION: planes_f / feat_f / img4 and the voxel levels are read as the last frame that encoded into these buffers left
+        // them.  Nothing of the encoder or the folds is enqueued and none of their events (ev_enc, ev_fold, ev_mid, ev_lev) is waited for: this frame
+        // did not record them, and the encoding frame's gather -- ahead of this frame on the caller's stream -- already waited for them.
+        const bool reuse = (f->flags & SHERF_FRAME_REUSE_OBSERVATION) != 0;
         // ---- a7-a9 per-frame SMPL tables: first needed by the warp (after sampling), so with an aux stream they queue there
         // behind the table folds and level builds and the encoder chain starts at once on the side stream ----
         auto smpl_tables = [&](sherf_stream_t st) -> int {
@@ -202,7 +206,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             return SHERF_OK;
         };
         if (!stream_aux) SHERF_RUN(smpl_tables(stream_side));
-        const int stagger = f->main_after_layer;
+        const int stagger = reuse ? -1 : f->main_after_layer;       // (nothing to stagger against)
         const int half_tables = (f->flags & SHERF_FRAME_HALF_TABLES) ? 1 : 0;      // folded tables + voxel rows in fp16 (the image stays fp32)
         auto fold_tables = [&](sherf_stream_t st) -> int {      // per-frame table re-layout (channel-last, projections folded in)
             SHERF_RUN(sherf_fold_tables(f->planes, f->Wa_t, f->planes_f, f->P * f->P, 3, 32, (int64_t)f->P * f->P * 32, half_tables, st));
@@ -212,11 +216,19 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         SHERF_CAP_TRACE("fold tables on aux");
         if (stream_aux) {       // independent of rays and voxels: off the ray side's chain, ahead of the level builds
             SHERF_HIP_CHECK(hipStreamWaitEvent(as_stream(stream_aux), d.ev_start, 0));
-            SHERF_RUN(fold_tables(stream_aux));
-            SHERF_HIP_CHECK(hipEventRecord(d.ev_fold, as_stream(stream_aux)));
+            if (reuse) {        // the SMPL tables otherwise ride inside the encoder's enqueue (smpl_on_aux below)
+                SHERF_RUN(smpl_tables(stream_aux));
+            } else {
+                SHERF_RUN(fold_tables(stream_aux));
+                SHERF_HIP_CHECK(hipEventRecord(d.ev_fold, as_stream(stream_aux)));
+            }
         }
         const size_t ncell1 = (size_t)SHERF_MAX_CELLS + 1;
         auto enqueue_encoder = [&]() -> int {        // ---- side: a11 sparse voxel encoder ----
+            if (reuse) {
+                SHERF_PROF(2, side);                 // (the timeline's "encoder done" stays readable: right behind the frame's start)
+                return SHERF_OK;
+            }
             const std::function<int()> smpl_on_aux = [&]() -> int { return smpl_tables(stream_aux); };
             SHERF_RUN(sherf_svox_encode_impl(f->vox_plan, f->vox_coord, f->vox_feat, f->vox_n, f->vox_training, levels, stream_side,
                                              stagger >= 0 ? d.ev_mid : nullptr, stagger, stream_aux, d.ev_lev,
@@ -266,10 +278,10 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         SHERF_CAP_TRACE("encoder");
         if (!encoder_first) SHERF_RUN(enqueue_encoder());
         SHERF_CAP_TRACE("encoder queued");
-        if (!stream_aux) SHERF_RUN(fold_tables(stream_main));
+        if (!stream_aux && !reuse) SHERF_RUN(fold_tables(stream_main));
         // ---- main: a8-a10 warp, a10-a12 gather, a13-a14 MLP ----
         SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_smpl, 0));
-        if (stream_aux) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_fold, 0));
+        if (stream_aux && !reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_fold, 0));
         int64_t cap = tok_cap;
         if (exact) {
             SHERF_HOST_STAMP(xp, "count wait begins");
@@ -297,7 +309,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                               !(g_sherf_debug & (1 << 25)) && !split_form && nparts <= 1 && !(f->gather_split & 7) && !(g_sherf_debug & (2048 | (1 << 29)));
         if (nparts > 1 && !(f->gather_split & 1) && !split_form) {
             SHERF_PROF(3, main);
-            SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
+            if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
             for (int k = 0; k < nparts; ++k) {
                 SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
                                               levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 0 | gv | (k << 8) | (nparts << 16), cap,
@@ -321,13 +333,13 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                                           nullptr, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 1 | gv, cap, f->tokens,
                                           f->extras, stream_main));
             SHERF_PROF(3, main);
-            SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
+            if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
             SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
                                           levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 2 | gv, cap, f->tokens,
                                           f->extras, stream_main));
         } else {
             SHERF_PROF(3, main);
-            SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
+            if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
             if (pe_frags)
                 SHERF_RUN(sherf_gather_tokens_pe(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
                                                  levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 0 | gv, cap, f->tokens,
@@ -409,6 +421,7 @@ uint64_t g_graph_clock = 0;
 int g_graph_on = -1;                  // -1: read SHERF_FRAME_GRAPH at the first frame
 bool g_graph_aux_ok = false;          // SHERF_FRAME_GRAPH_AUX=1: capture three-stream frames too (crashes the runtime on this box: see sherf_render_frame)
 int64_t g_graph_stats[4] = {0, 0, 0, 0};   // captures, replays, eager frames, failed captures
+int64_t g_obs_stats[2] = {0, 0};           // frames whose phase 1 encoded the observation / reused it (SHERF_FRAME_REUSE_OBSERVATION); guarded by g_frame_mu
 
 inline void fnv(uint64_t& h, const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -439,12 +452,26 @@ extern "C" int sherf_frame_graph_stats(int64_t* stats_host, int32_t n) {
     return SHERF_OK;
 }
 
+extern "C" int sherf_frame_observation_stats(int64_t* stats_host, int32_t n) {
+    SHERF_CHECK_ARG(stats_host && n >= 2);
+    std::lock_guard<std::mutex> frame_lock(g_frame_mu);
+    for (int i = 0; i < 2; ++i) stats_host[i] = g_obs_stats[i];
+    return SHERF_OK;
+}
+
 extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
                                   sherf_stream_t stream_side, sherf_stream_t stream_aux) {
     SHERF_CHECK_ARG(f && levels && ((phase & 3) || phase == 4) && stream_side != stream_main && (!stream_aux || (stream_aux != stream_main && stream_aux != stream_side)));
     SHERF_CHECK_ARG((f->white_back & ~(SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS)) == 0);
     SHERF_CHECK_ARG(!(f->mlp_prec & SHERF_MLP_OSG_DECODER) || f->wstream);          // (the OSG weight block: include/sherf_hip.h)
+    if (phase != 4 && (phase & 1) && (f->flags & SHERF_FRAME_REUSE_OBSERVATION)) {
+        // `levels` is an input here: it must be what an encoding frame's call wrote for THIS plan (csrc/svox.hip: rows = the plan's folded rows)
+        SHERF_CHECK_ARG(f->vox_plan && f->planes_f && f->feat_f && f->img4);
+        for (int i = 0; i < 3; ++i)
+            SHERF_CHECK_ARG(levels[i].wp && levels[i].rows && levels[i].rows == f->vox_plan->fold_rows[i] && levels[i].D > 0 && levels[i].H > 0 && levels[i].W > 0);
+    }
     std::lock_guard<std::mutex> frame_lock(g_frame_mu);
+    if (phase != 4 && (phase & 1)) ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
     if (g_graph_on < 0) {
         const char* e = getenv("SHERF_FRAME_GRAPH");
         g_graph_on = (e && atoi(e) != 0) ? 1 : 0;                     // OFF unless asked for: see the note above sherf_render_frame

@@ -178,6 +178,12 @@ class _Workspace:
         self.desc = None
         self.stacked = None
         self.tok_cap = 0
+        # what the folded tables (planes_f / feat_f / img4) and the plan's voxel levels currently hold (rendering option `reuse_observation`):
+        # the key of the last frame that encoded into them, the `levels` array that frame's native call filled in, and the keyed tensors
+        # (kept referenced: a freed address cannot come back and compare equal)
+        self.obs_key = None
+        self.obs_levels = None
+        self.obs_refs = None
 
     def frame(self, R, S, cap, dev):
         key = (R, S, cap, str(dev))
@@ -204,6 +210,7 @@ class _Workspace:
         self.key, self.t = key, t
         self.desc = None
         self.tok_cap = 0
+        self.obs_key = None                               # (a re-sized workspace never reuses what the old one held)
         self.tokens(min(cap, 256), dev)                   # (placeholders until the frame's own count is known: renderer._token_capacity)
         return t
 
@@ -331,6 +338,9 @@ class ImportanceRenderer(nn.Module):
     # beside `enable_autograd` (set per instance, or for the class by sherf_amd.install()): a renderer built with use_NeRF_decoder=False records its
     # grad-enabled forwards for the HIP backward only when this is set too -- the OSG backward is staged
     enable_osg_autograd = False
+    # default of rendering_options['reuse_observation']: frame N + 1 of a camera / pose sweep renders from the folded tables and voxel levels frame N left
+    # in the workspace when every input they are a function of is unchanged (_observation_key); opt-in
+    reuse_observation = False
 
     def __init__(self, use_1d_feature=True, use_2d_feature=True, use_3d_feature=True, use_trans=False, use_NeRF_decoder=False,
                  smpl=None, smpl_path=os.path.join('assets', 'SMPL_NEUTRAL.pkl'), mlp_precision='auto', table_precision='auto', encoder_precision='auto'):
@@ -1027,6 +1037,30 @@ class ImportanceRenderer(nn.Module):
             return choice
         return decide
 
+    # ---- reuse of the encoded observation across the frames of a sweep ---------------------------------------------------------
+    def _observation_key(self, wsp, wc, pl, cfg, planes, obs_input_feature, obs_input_img, sp, obs_sp_input, tables):
+        """-> (key, refs): everything the folded tables (planes_f / feat_f / img4) and the plan's voxel levels are a function of.  Two frames with equal
+        keys on one workspace fold and encode the same bits, so the second may render from what the first left (csrc/frame.hip,
+        SHERF_FRAME_REUSE_OBSERVATION).  Input tensors by identity, address and version counter; the weights through the caches that already track
+        them -- `_weights` (the projections behind Wa_t / Wb_t / the fold matrices / tok_bias), the encoder's packed weights and its plan, in eval mode
+        the running statistics `prepare` folded into the plan; the resolved table / encoder precision and the encoder's mode; the buffers themselves.
+        `refs` keeps every keyed tensor alive while the key is recorded: a freed address cannot come back at version 0 and compare equal.
+        (A write that does not bump `_version` -- through a raw pointer, `.data`, another process -- cannot be seen: INTEGRATION.md.)"""
+        ident = lambda t: (id(t), t.data_ptr(), t._version)
+        enc = self.encoder_3d
+        inputs = (planes, obs_input_feature, obs_input_img, sp.features, sp.indices, obs_sp_input['bounds'])
+        packed = (wc['Wa_t'], wc['Wb_t'], wc['tok_bias']) + tuple(wc['fold'])
+        key = (id(self), tuple([ident(t) for t in inputs]), tuple([int(v) for v in obs_sp_input['out_sh']]),
+               wc['key'], tuple([ident(t) for t in packed]),
+               id(pl), pl['key'], None if enc.training else pl.get('eval_key'), bool(enc.training), cfg[1], cfg[2],
+               id(wsp.t), tuple([(t.data_ptr(), tuple(t.shape)) for t in tables]))
+        return key, (inputs, packed, pl, tables, wsp.t)
+
+    def observation_stats(self):
+        """(frames of this renderer that encoded their observation, frames that reused it): rendering option `reuse_observation`."""
+        st = self.__dict__.get('_obs_stats') or (0, 0)
+        return int(st[0]), int(st[1])
+
     # ---- forward -----------------------------------------------------------------------------
     def forward(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
                 decoder, ray_origins, ray_directions, near, far, input_data, rendering_options):
@@ -1219,6 +1253,22 @@ class ImportanceRenderer(nn.Module):
         fr.white_back = _lib.composite_bits(opts.get('white_back', False), clamp_mode)     # bit 0: white background, bit 1: softplus
         fr.main_after_layer = int(opts.get('main_after_layer', self.main_after_layer))
         noise = float(opts.get('density_noise', 0) or 0)
+        # rendering option `reuse_observation`: the native flag is set only when this frame's observation key equals the one the workspace recorded
+        # for what its tables and voxel levels hold; any difference encodes as always and records the new key.  Never for a grad-recorded forward
+        # (its backward reads this frame's own tables) nor for a calibration frame of mlp_precision='auto' (it renders through other precisions).
+        recorded = (torch.is_grad_enabled() and getattr(self, 'enable_autograd', False)) or getattr(self, '_in_autograd', False)
+        want_reuse = bool(opts.get('reuse_observation', getattr(self, 'reuse_observation', False))) and not recorded
+        obs_key = obs_refs = None
+        reused = False
+        if want_reuse:
+            obs_key, obs_refs = self._observation_key(wsp, wc, pl, cfg, planes, obs_input_feature, obs_input_img, canonical_sp_conv_volume, obs_sp_input,
+                                                      (planes_f, feat_f, img4))
+            reused = not calibrate and wsp.obs_key is not None and wsp.obs_key == (obs_key, wsp.tok_cap)
+        if reused:
+            fr.flags |= _lib.FRAME_REUSE_OBSERVATION
+            levels = wsp.obs_levels                                      # an INPUT of the native call under the flag: the encoding frame's array
+        else:
+            wsp.obs_key = None                                           # (until this frame's own encode has been enqueued)
         decide = None
         if calibrate and noise == 0:
             decide = self._calibrate(fr, decoder, dev, ws, levels, (s_main, s_side, s_aux), exact)
@@ -1260,6 +1310,12 @@ class ImportanceRenderer(nn.Module):
                     decide = None
                     self._wcache['auto'] = None
                 enqueue()
+        if want_reuse:
+            if not reused:
+                wsp.obs_levels, wsp.obs_refs = levels, obs_refs
+            wsp.obs_key = (obs_key, wsp.tok_cap)
+        st_obs = self.__dict__.setdefault('_obs_stats', [0, 0])
+        st_obs[1 if reused else 0] += 1
         if static_out:
             out = out.clone()
         if self.__dict__.get('_form_auto') and not calibrate and noise == 0 and self._form_key(dev, cfg[0], fr) not in self._FORM_CHOICE and cfg[0] != 'f16x3' \
@@ -1284,5 +1340,6 @@ class ImportanceRenderer(nn.Module):
                                   bounds=input_data['t_world_bounds'], vox_min=vox_min.reshape(-1)[:3], vox_sh=[int(v) for v in obs_sp_input['out_sh']],
                                   coord=vcoord, H=H, W=W, white_back=bool(opts.get('white_back', False)), clamp_mode=clamp_mode))
         self.last['out'] = out
+        self.last['observation_reused'] = reused
         return ws['rgb'].view(1, R, 3), ws['depth'].view(1, R, 1), ws['acc'].view(1, R, 1)
 

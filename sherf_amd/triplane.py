@@ -208,6 +208,7 @@ class TriPlaneGenerator(nn.Module):
         state = dict(self.__dict__)
         state['_graphed'] = {}
         state.pop('_out_sh_memo', None)
+        state.pop('_obs_cache', None)                    # (cache_observation: device tensors of one subject, dropped like the graphs)
         return state
 
     def _producer(self, name, module, fn):
@@ -309,8 +310,56 @@ class TriPlaneGenerator(nn.Module):
         out_sh, _ = torch.max(out_sh, dim=0)
         return {'coord': coord, 'out_sh': out_sh.tolist(), 'batch_size': sh[0], 'bounds': bounds}, None
 
+    # ---- the observation side of a frame, cached across a camera / pose sweep -------------------------------------------------------
+    def _observation_key(self, input_data, call):
+        """What everything `synthesis` builds from the observation alone is a function of: the observation inputs (identity, address, version
+        counter) and every parameter and buffer of the generator outside renderer.encoder_3d's BatchNorm running buffers (those move with every
+        train-mode frame and reach the image through the renderer, which keys them itself).  `call`: the scalar arguments of the call that reach
+        the mapping network / the backbone.  -> (key, the keyed tensors: kept alive beside the cache so that no address comes back)."""
+        from .renderer import fast_params, state_key
+        tensors = [input_data['obs_img_all'], input_data['obs_vertices'], input_data['obs_R_all'], input_data['obs_T_all'], input_data['obs_K_all'],
+                   input_data['t_vertices']]
+        for name in ('obs_params', 't_params'):
+            tensors += [input_data[name][k] for k in sorted(input_data[name])]
+        ps = []
+        for name, m in self._modules.items():
+            if m is None:
+                continue
+            if m is not self.renderer:
+                fast_params(m, ps, buffers=True)
+                continue
+            for p in m._parameters.values():
+                if p is not None:
+                    ps.append(p)
+            for rn, rm in m._modules.items():
+                if rm is not None:
+                    fast_params(rm, ps, buffers=rm is not m.encoder_3d)
+        key = (tuple([(id(t), t.data_ptr(), t._version) for t in tensors]), state_key(ps), call)
+        return key, tensors
+
+    @staticmethod
+    def _observation_call(update_emas, kwargs):
+        """The non-tensor arguments of a synthesis call that reach the producers (noise_mode, ...), as part of the cache key."""
+        plain = (str, int, float, bool, type(None))
+        return (bool(update_emas), tuple(sorted((k, v if isinstance(v, plain) else id(v)) for k, v in kwargs.items())))
+
+    @property
+    def observation_cache_stats(self):
+        """{'hits', 'misses'} of `use_cached_observation` since construction."""
+        return dict(self.__dict__.setdefault('_obs_cache_stats', dict(hits=0, misses=0)))
+
+    def _cached_observation(self, key, ws=None, planes=None):
+        """The cache `cache_observation` filled, if it is still valid under `key` (and, given explicitly, for these `ws` / `planes`), else None."""
+        oc = self.__dict__.get('_obs_cache')
+        if oc is None or torch.is_grad_enabled():
+            return None
+        if oc['key'] != key or (ws is not None and ws is not oc['ws']) or (planes is not None and planes is not oc['planes_arg']):
+            return None
+        return oc
+
     def synthesis(self, ws, input_data, c, neural_rendering_resolution=None, use_sr_module=True, update_emas=False,
-                  cache_backbone=False, use_cached_backbone=False, test_flag=False, planes=None, **synthesis_kwargs):
+                  cache_backbone=False, use_cached_backbone=False, test_flag=False, planes=None, cache_observation=False,
+                  use_cached_observation=False, **synthesis_kwargs):
         if neural_rendering_resolution is None:
             neural_rendering_resolution = self.neural_rendering_resolution
         else:
@@ -318,25 +367,52 @@ class TriPlaneGenerator(nn.Module):
         ray_origins, ray_directions = input_data['ray_o_all'][:, 0], input_data['ray_d_all'][:, 0]
         near, far = input_data['near_all'][:, 0], input_data['far_all'][:, 0]
         N, M, _ = ray_origins.shape
-        if planes is None:
-            if use_cached_backbone and self._last_planes is not None:
-                planes = self._last_planes
-            else:
-                planes = self._producer('backbone.synthesis', self.backbone.synthesis, self.backbone.synthesis)(ws, update_emas=update_emas, **synthesis_kwargs)
-        if cache_backbone:
-            self._last_planes = planes
-        obs_input_img = input_data['obs_img_all'][:, 0]
-        obs_input_feature = self._producer('encoder_2d_feature', self.encoder_2d_feature, self.encoder_2d_feature)(obs_input_img, extract_feature=True)
-        fused = self.fused_glue and not torch.is_grad_enabled() and obs_input_img.shape[0] == 1
-        f3d, mask = (self.fused_vertex_features if fused else self.vertex_features)(input_data, obs_input_img, obs_input_feature)
-        can = self.canonical_obs_vertices(input_data)
-        sp_input, _ = (self.fused_prepare_sp_input if fused else self.prepare_sp_input)(input_data['t_vertices'].float(), can)
-        sp = SparseConvTensor(f3d.reshape(-1, f3d.shape[-1]), sp_input['coord'], sp_input['out_sh'], sp_input['batch_size'])
-        planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+        # cache_observation / use_cached_observation (beside and independent of cache_backbone / use_cached_backbone): everything below that depends
+        # on the observation alone -- planes, feature map, vertex features and mask, canonical observed vertices, voxelisation -- is kept as the very
+        # tensor objects the renderer saw, so that its own observation key matches and the frame renders from the tables and voxel levels already in
+        # its workspace (rendering option `reuse_observation`, turned on for these calls).  Never while a gradient is being recorded.
+        nograd = not torch.is_grad_enabled()
+        caching = (cache_observation or use_cached_observation) and nograd
+        if caching:
+            # (taken BEFORE any producer runs: a producer in training mode moves its own BatchNorm buffers, so its frames never hit)
+            key, key_refs = self.__dict__.pop('_obs_key_memo', None) or self._observation_key(input_data, self._observation_call(update_emas, synthesis_kwargs))
+        oc = self._cached_observation(key, ws, planes) if use_cached_observation and nograd else None
+        if use_cached_observation and nograd:
+            st = self.__dict__.setdefault('_obs_cache_stats', dict(hits=0, misses=0))
+            st['hits' if oc is not None else 'misses'] += 1
+        if oc is not None:
+            planes, obs_input_img, obs_input_feature, sp, mask, sp_input = (oc[k] for k in ('planes', 'obs_input_img', 'obs_input_feature', 'sp', 'mask', 'sp_input'))
+            if cache_backbone:
+                self._last_planes = oc['planes_raw']
+        else:
+            planes_arg = planes
+            if planes is None:
+                if use_cached_backbone and self._last_planes is not None:
+                    planes = self._last_planes
+                else:
+                    planes = self._producer('backbone.synthesis', self.backbone.synthesis, self.backbone.synthesis)(ws, update_emas=update_emas, **synthesis_kwargs)
+            if cache_backbone:
+                self._last_planes = planes
+            planes_raw = planes
+            obs_input_img = input_data['obs_img_all'][:, 0]
+            obs_input_feature = self._producer('encoder_2d_feature', self.encoder_2d_feature, self.encoder_2d_feature)(obs_input_img, extract_feature=True)
+            fused = self.fused_glue and not torch.is_grad_enabled() and obs_input_img.shape[0] == 1
+            f3d, mask = (self.fused_vertex_features if fused else self.vertex_features)(input_data, obs_input_img, obs_input_feature)
+            can = self.canonical_obs_vertices(input_data)
+            sp_input, _ = (self.fused_prepare_sp_input if fused else self.prepare_sp_input)(input_data['t_vertices'].float(), can)
+            sp = SparseConvTensor(f3d.reshape(-1, f3d.shape[-1]), sp_input['coord'], sp_input['out_sh'], sp_input['batch_size'])
+            planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+            if caching:                                                            # (a miss refills)
+                self.__dict__['_obs_cache'] = dict(key=key, refs=key_refs, ws=ws, planes_arg=planes_arg, planes_raw=planes_raw, planes=planes, obs_input_img=obs_input_img,
+                                                   obs_input_feature=obs_input_feature, vertex_features=f3d, mask=mask, canonical_obs_vertices=can,
+                                                   sp_input=sp_input, sp=sp)
         if test_flag:
             self.rendering_kwargs.update({'density_noise': 0})
+        opts = self.rendering_kwargs
+        if caching:
+            opts = dict(opts, reuse_observation=True)
         rgb, depth, acc = self.renderer(planes, obs_input_img, obs_input_feature, sp, mask, sp_input, self.decoder, ray_origins,
-                                        ray_directions, near, far, input_data, self.rendering_kwargs)
+                                        ray_directions, near, far, input_data, opts)
         H, W = input_data['obs_img_all'].shape[-2:]
         feature_image = rgb.permute(0, 2, 1).reshape(N, rgb.shape[-1], H, W).contiguous()
         depth_image = depth.permute(0, 2, 1).reshape(N, 1, H, W)
@@ -352,10 +428,34 @@ class TriPlaneGenerator(nn.Module):
         return {'image': sr_image, 'image_raw': rgb_image, 'image_depth': depth_image, 'weights_image': weights_image}
 
     def forward(self, input_data, z, c, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None, use_sr_module=True,
-                update_emas=False, cache_backbone=False, use_cached_backbone=False, test_flag=False, **synthesis_kwargs):
-        input_img = input_data['obs_img_all'][:, 0]
-        ws = self.mapping(z, c, input_img=input_img, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff,
-                          update_emas=update_emas)
-        return self.synthesis(ws, input_data, c, update_emas=update_emas, neural_rendering_resolution=neural_rendering_resolution,
-                              use_sr_module=use_sr_module, cache_backbone=cache_backbone, use_cached_backbone=use_cached_backbone,
-                              test_flag=test_flag, **synthesis_kwargs)
+                update_emas=False, cache_backbone=False, use_cached_backbone=False, test_flag=False, cache_observation=False,
+                use_cached_observation=False, **synthesis_kwargs):
+        # use_cached_observation: `ws` is a function of the observation image alone (the code comes from encoder_2d; `c` only where the
+        # conditioning is neither zeroed nor scaled away) -- a valid cache serves it and neither encoder_2d nor the mapping network runs
+        kw = self.rendering_kwargs
+        c_counts = not kw.get('c_gen_conditioning_zero', True) and kw.get('c_scale', 0) != 0
+        mapping_call = (truncation_psi, truncation_cutoff, (id(c), c.data_ptr(), c._version) if c_counts else None)
+        oc = None
+        self.__dict__.pop('_obs_key_memo', None)
+        if (cache_observation or use_cached_observation) and not torch.is_grad_enabled():
+            # (one walk of the parameters per call: synthesis takes the key from here)
+            memo = self.__dict__['_obs_key_memo'] = self._observation_key(input_data, self._observation_call(update_emas, synthesis_kwargs))
+            if use_cached_observation:
+                oc = self._cached_observation(memo[0])
+        try:
+            if oc is not None and oc.get('mapping_call') == mapping_call:
+                ws = oc['ws']
+            else:
+                input_img = input_data['obs_img_all'][:, 0]
+                ws = self.mapping(z, c, input_img=input_img, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff,
+                                  update_emas=update_emas)
+            out = self.synthesis(ws, input_data, c, update_emas=update_emas, neural_rendering_resolution=neural_rendering_resolution,
+                                 use_sr_module=use_sr_module, cache_backbone=cache_backbone, use_cached_backbone=use_cached_backbone,
+                                 test_flag=test_flag, cache_observation=cache_observation, use_cached_observation=use_cached_observation,
+                                 **synthesis_kwargs)
+        finally:
+            self.__dict__.pop('_obs_key_memo', None)
+        oc = self.__dict__.get('_obs_cache')
+        if oc is not None and oc['ws'] is ws:
+            oc['mapping_call'], oc['c'] = mapping_call, (c if c_counts else None)
+        return out
