@@ -36,7 +36,12 @@ def composite_backward(renderer, d_rgb, d_acc, ray_directions, near, far, white_
     ws, R, S, cap = last['ws'], last['R'], last['S'], last['cap']
     f32 = lambda t, *shape: t.detach().to(dtype=torch.float32).contiguous().view(*shape)
     P = _lib.ptr
-    nv = int(ws['counters'][0])                                   # (the forward is long done: the loss has been formed from its output)
+    nv, _, _, flags = ws['counters'][:4].tolist()                 # (the forward is long done: the loss has been formed from its output)
+    if flags & 2:
+        # the kernel walks every ray's base .. base + count; sample_out has only `cap` rows (a no-grad forward sizes the token workspace from the
+        # frame's count or a given number; a training forward sizes it for the worst case and cannot get here)
+        raise RuntimeError(f'composite_backward: the forward overflowed its token workspace ({cap} rows for {nv} valid samples; its rays beyond the '
+                           f'capacity are NaN): render the frame again with a token workspace re-sized from counters[0] = {nv} before a backward')
     # rows of the frame's valid samples only: the kernel touches rows < nv (every ray's base + count lies below it), and the buffer used to be
     # capacity = R x S rows -- a 268 MB zero fill per step at 512 x 512 x 64 for 12 MB of gradient
     out = torch.zeros(max(nv, 1), 4, device=ws['sample_out'].device)
@@ -57,6 +62,8 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
         raise RuntimeError('render_backward needs a preceding forward call')
     ws, pl, b = last['ws'], last['plan'], last['bwd']
     dev = ws['sample_out'].device
+    # ---- a16 ----  (first: it refuses a frame whose forward overflowed its token workspace before anything is launched)
+    d_sample = composite_backward(renderer, d_rgb, d_acc, b['ray_d'], b['near'], b['far'], b['white_back'], b.get('clamp_mode', 'relu')).contiguous()
     f32 = lambda t: t.detach().to(dtype=torch.float32).contiguous()
     state = {'renderer.' + k: v for k, v in renderer.state_dict().items()}
     state.update({'decoder.' + k: v for k, v in decoder.state_dict().items()})
@@ -67,8 +74,6 @@ def render_backward(renderer, decoder, d_rgb, d_acc):
         Wr, br = renderer._effective_reprojection()
         state['renderer.conv1d_reprojection.weight'], state['renderer.conv1d_reprojection.bias'] = Wr[:, :, None], br
     ops = HipOps()
-    # ---- a16 ----
-    d_sample = composite_backward(renderer, d_rgb, d_acc, b['ray_d'], b['near'], b['far'], b['white_back'], b.get('clamp_mode', 'relu')).contiguous()
     n = d_sample.shape[0]
     if n == 0:
         raise RuntimeError('render_backward: no valid sample in the last frame')

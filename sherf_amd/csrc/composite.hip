@@ -141,9 +141,13 @@ __global__ void __launch_bounds__(256) composite_dense_kernel(const float* __res
 //   g_w[k] = g_c . c_k + dL/dacc - white_back * sum(g_c):
 //   dL/dc_k     = g_c w_k
 //   dL/dalpha_k = g_w[k] T_k - (sum_{m>k} g_w[m] w_m) / (1 - alpha_k + 1e-10)        (T_m carries the factor of sample k)
+//               = T_k (g_w[k] - Q_k),   Q_k = sum_{m>k} g_w[m] alpha_m prod_{k<j<m} f_j,   f_j = 1 - alpha_j + 1e-10
 //   dL/dsigma_k = dL/dalpha_k * delta_k * exp(-s_k delta_k) * ds_k/dsigma_k,   s = relu(sigma): [sigma_k > 0];  s = softplus(sigma - 1): z / (z + 1)
-// Two forward sweeps over the ray's compact samples: the first takes the total of g_w w, the second rebuilds T, alpha, w
-// and turns the running prefix into the suffix sum.  Same thread-per-ray shape and traffic class as the forward.
+// Two sweeps over the ray's compact samples.  The first runs BACKWARDS and builds Q by its recurrence Q_{k-1} = g_w[k] alpha_k + f_k Q_k (Q behind
+// the last sample is 0), leaving Q_k in the .w of the sample's output row; the second runs forwards, rebuilds T, alpha, w and overwrites the row.
+// (Until the per-ray edge tests, the suffix sum was `total - prefix` of two forward sweeps, divided by f_k: behind an exactly opaque sample both are
+// O(1) while the suffix is O(1e-10), so the difference was rounding noise, 1e-10 of it a division by 1e-10 later -- gradients of the samples behind
+// the opaque one wrong by several times their size.  Q needs no difference and no division.)  Same thread-per-ray shape as the forward.
 template <int MODE>
 __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_t* __restrict__ ray_base, const int32_t* __restrict__ ray_cnt,
                                                                     const int32_t* __restrict__ cs_idx, const float4* __restrict__ sample_out,
@@ -159,18 +163,17 @@ __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_
     const int base = ray_base[r], cnt = ray_cnt[r];
     const float gx = 2.f * d_rgb[r * 3], gy = 2.f * d_rgb[r * 3 + 1], gz = 2.f * d_rgb[r * 3 + 2];
     const float gconst = d_acc[r] - (white_back ? gx + gy + gz : 0.f);
-    float T = 1.f, total = 0.f;
-    for (int i = 0; i < cnt; ++i) {
+    float Q = 0.f;
+    for (int i = cnt - 1; i >= 0; --i) {
         const int k = cs_idx[base + i] - r * S;
         const float4 o = sample_out[base + i];
         const float t = depth_at(nr, range, k, S);
         const float delta = (k == S - 1 ? 1e10f : depth_at(nr, range, k + 1, S) - t) * dn;
         const float alpha = 1.f - expf(-(density<MODE>(o.w) * delta));
-        total += (gx * o.x + gy * o.y + gz * o.z + gconst) * (alpha * T);
-        T = T * (1.f - alpha + 1e-10f);
+        d_sample_out[base + i].w = Q;
+        Q = (gx * o.x + gy * o.y + gz * o.z + gconst) * alpha + (1.f - alpha + 1e-10f) * Q;
     }
-    T = 1.f;
-    float prefix = 0.f;
+    float T = 1.f;
     for (int i = 0; i < cnt; ++i) {
         const int k = cs_idx[base + i] - r * S;
         const float4 o = sample_out[base + i];
@@ -179,8 +182,7 @@ __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_
         const float e = expf(-(density<MODE>(o.w) * delta));
         const float alpha = 1.f - e, w = alpha * T;
         const float gw = gx * o.x + gy * o.y + gz * o.z + gconst;
-        prefix += gw * w;
-        const float dalpha = gw * T - (total - prefix) / (1.f - alpha + 1e-10f);
+        const float dalpha = T * (gw - d_sample_out[base + i].w);
         const float dsigma = MODE == CLAMP_RELU ? (o.w > 0.f ? dalpha * delta * e : 0.f) : dalpha * delta * e * density_grad<MODE>(o.w);
         d_sample_out[base + i] = make_float4(gx * w, gy * w, gz * w, dsigma);
         T = T * (1.f - alpha + 1e-10f);
@@ -193,10 +195,10 @@ __global__ void __launch_bounds__(256) composite_compact_bwd_kernel(const int32_
 // empty ray -- here the ray's depth term is dropped):
 //   g_w[k]      = g_c . c_k - white_back * sum(g_c) + dL/dw_k + (g_d / W) (t_k - depth)
 //   dL/dc_k     = g_c w_k
-//   dL/dalpha_k = g_w[k] T_k - (sum_{m>k} g_w[m] w_m) / (1 - alpha_k + 1e-10)
+//   dL/dalpha_k = g_w[k] T_k - (sum_{m>k} g_w[m] w_m) / (1 - alpha_k + 1e-10) = T_k (g_w[k] - Q_k)                (Q: see the compact backward)
 //   dL/dsigma_k = dL/dalpha_k * delta_k * exp(-s_k delta_k) * ds_k/dsigma_k
-// Two forward sweeps, one thread per ray: the first takes W, D and the total of the depth-free part of g_w w; the second rebuilds T, alpha, w and
-// keeps the three running prefixes in the first sweep's order, so that every suffix (total - prefix) is exactly 0 behind the last sample.
+// Three sweeps, one thread per ray: forwards for W and D (the depth and whether it is live), backwards for Q (left in d_sigma[k]), forwards again to
+// rebuild T, alpha, w and write the gradients.  No suffix is taken as a difference of totals.
 // A null upstream gradient is zero.  No gradient w.r.t. depths / rays_d.
 template <int MODE>
 __global__ void __launch_bounds__(256) composite_dense_bwd_kernel(const float* __restrict__ colors, const float* __restrict__ sigma,
@@ -218,31 +220,37 @@ __global__ void __launch_bounds__(256) composite_dense_bwd_kernel(const float* _
     float* ds = d_sigma + (size_t)r * S;
     const float gx = d_rgb ? 2.f * d_rgb[r * 3] : 0.f, gy = d_rgb ? 2.f * d_rgb[r * 3 + 1] : 0.f, gz = d_rgb ? 2.f * d_rgb[r * 3 + 2] : 0.f;
     const float gconst = white_back ? -(gx + gy + gz) : 0.f;
-    float T = 1.f, total = 0.f, wsum = 0.f, dsum = 0.f;
+    float T = 1.f, wsum = 0.f, dsum = 0.f;
     for (int k = 0; k < S; ++k) {
         const float t = tt[k];
         const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
         const float alpha = 1.f - expf(-(density<MODE>(sg[k]) * delta));
         const float w = alpha * T;
         T = T * (1.f - alpha + 1e-10f);
-        const float base = gx * c[k * 3] + gy * c[k * 3 + 1] + gz * c[k * 3 + 2] + gconst + (dw ? dw[k] : 0.f);
-        total += base * w; wsum += w; dsum += w * t;
+        wsum += w; dsum += w * t;
     }
     const float dep = dsum / wsum;
     const bool live = d_depth && dep == dep && dep >= dmin && dep <= dmax;
     const float gdw = live ? d_depth[r] / wsum : 0.f;
+    float Q = 0.f;
+    for (int k = S - 1; k >= 0; --k) {
+        const float t = tt[k];
+        const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
+        const float alpha = 1.f - expf(-(density<MODE>(sg[k]) * delta));
+        const float base = gx * c[k * 3] + gy * c[k * 3 + 1] + gz * c[k * 3 + 2] + gconst + (dw ? dw[k] : 0.f);
+        const float gw = live ? base + gdw * (t - dep) : base;
+        ds[k] = Q;
+        Q = gw * alpha + (1.f - alpha + 1e-10f) * Q;
+    }
     T = 1.f;
-    float ptotal = 0.f, pw = 0.f, pd = 0.f;
     for (int k = 0; k < S; ++k) {
         const float t = tt[k];
         const float delta = (k == S - 1 ? 1e10f : tt[k + 1] - t) * dn;
         const float e = expf(-(density<MODE>(sg[k]) * delta));
         const float alpha = 1.f - e, w = alpha * T;
         const float base = gx * c[k * 3] + gy * c[k * 3 + 1] + gz * c[k * 3 + 2] + gconst + (dw ? dw[k] : 0.f);
-        ptotal += base * w; pw += w; pd += w * t;
         const float gw = live ? base + gdw * (t - dep) : base;
-        const float suffix = live ? (total - ptotal) + gdw * ((dsum - pd) - dep * (wsum - pw)) : total - ptotal;
-        const float dalpha = gw * T - suffix / (1.f - alpha + 1e-10f);
+        const float dalpha = T * (gw - ds[k]);
         const float dg = density_grad<MODE>(sg[k]);
         ds[k] = dg == 0.f ? 0.f : dalpha * delta * e * dg;          // (relu: the sigma > 0 mask, as a select -- not 0 * a product that may overflow)
         dc[k * 3] = gx * w; dc[k * 3 + 1] = gy * w; dc[k * 3 + 2] = gz * w;
