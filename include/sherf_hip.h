@@ -519,6 +519,47 @@ typedef struct {
 } sherf_frame;
 int sherf_render_frame(const sherf_frame* frame, int phase, sherf_vox_level* levels_out_host, sherf_stream_t stream_main,
                        sherf_stream_t stream_side, sherf_stream_t stream_aux);
+/* ---------------------------------------------------------------------------------------------
+ * Field query: sigma and rgb at caller-supplied 3-D points -- renderer.py:307-368 (SMPL-frame transform, nearest posed vertex + 5 cm shell mask, boolean-mask
+ * compaction in ascending point order, T2C / C2S warps, projection, the three taps, fusion, transformer, decoder, scatter-back) applied to
+ * `sample_coordinates` / `sample_directions` handed in instead of derived from rays: what TriPlaneGenerator.sample / sample_mixed declare
+ * (triplane.py:219-230; both stale there).  Inference only.  csrc/field.hip.
+ *
+ * sherf_points_mask_nn: sherf_sample_mask_nn for points[n][3] (world frame).  The points are laid out as rows of 64 -- row r = points 64 r .. 64 r + 63, the last
+ *   row ragged -- and a row takes a ray's place in every buffer: ray_base / ray_cnt [ceil(n / 64)], ray_mask [ceil(n / 64)] u64 (bit k of word r = point
+ *   64 r + k is within the shell), dense_vid [n], scan_ws [rows + rows / 1024 + 2].  For compact sample c: cs_idx[c] = the point's index, cs_vid[c], cs_xs[c][4];
+ *   ascending point order, deterministic.  counters[0] = the number of valid points; counters[1..2] (a frame's depth range) are left at their reset values.
+ *   cs_xs doubles as the candidate list: capacity >= n, 0 < n < 2^31, else SHERF_EINVAL before anything is launched.  Same cell list / near mask / near lists
+ *   as sherf_sample_mask_nn; x_s is evaluated by the same operations in the same order as there, so a point that equals a frame's o + t d in fp32 gets that
+ *   sample's bits. */
+int sherf_points_mask_nn(const float* points, int64_t n, const float* Rg, const float* Th, const float* grid_hdr,
+                         const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
+                         int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs,
+                         int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
+                         const uint16_t* near_list, sherf_stream_t stream);
+/* The scatter-back (renderer.py:364-368): for point i < n, rgb[i][3] / sigma[i] = sample_out[c] of its compact sample c (found from ray_mask / ray_base as
+ * sherf_points_mask_nn left them) and mask[i] = 1, or (0, 0, 0) / -80 / 0 where the shell mask failed.  One pass, every output element written once.  A valid
+ * point with c >= tok_cap (more valid points than sample_out holds) is written as NaN (mask 1) and counters[3] |= 2, as sherf_composite_compact_cap treats
+ * such a ray; sample_out is never read beyond tok_cap rows.  0 < n < 2^31, tok_cap > 0, non-null pointers, else SHERF_EINVAL. */
+int sherf_field_scatter(int32_t* counters, const uint64_t* ray_mask, const int32_t* ray_base, const float* sample_out,
+                        int64_t n, int64_t tok_cap, float* rgb, float* sigma, uint8_t* mask, sherf_stream_t stream);
+/* The whole query as ONE native call: phases 1 + 2 of sherf_render_frame on the same descriptor with sherf_points_mask_nn in the ray sampler's place, the
+ * warp reading dirs[point] and sherf_field_scatter in the compositing's place -- SMPL tables, cell and near lists, folds, encoder (or none of the last two
+ * under SHERF_FRAME_REUSE_OBSERVATION), gather and network in whichever launch form frame->flags / mlp_prec select.  Of the descriptor, ray_o / ray_d / near /
+ * far / R / S / white_back / rgb / depth / acc are ignored; capacity >= query->n sizes the sampler's buffers (cs_idx / cs_vid / cs_xs [capacity], dense_vid
+ * [n], the row buffers as above), tok_capacity the token side.  SHERF_FRAME_REPORT_COUNT / sherf_frame_count and the profiling ring (field [6]: the
+ * scatter-back done) work as for a frame; counted by sherf_frame_observation_stats like a frame; never captured as a graph. */
+typedef struct {
+    const float* points;        /* [n][3] world frame, as ray_origins */
+    const float* dirs;          /* [n][3] view directions */
+    int64_t n;
+    float* rgb;                 /* [n][3] */
+    float* sigma;               /* [n] */
+    uint8_t* mask;              /* [n] 1 = within 5 cm of a posed vertex */
+} sherf_field_query;
+int sherf_query_field(const sherf_frame* frame, const sherf_field_query* query, sherf_vox_level* levels_out_host,
+                      sherf_stream_t stream_main, sherf_stream_t stream_side, sherf_stream_t stream_aux);
+
 /* The valid-sample count of the last frame THE CALLING THREAD enqueued on the current device with SHERF_FRAME_REPORT_COUNT (waits for the
  * sampler of that frame, not for the frame; other threads' frames on the device have their own slots -- a ring of eight per device -- and the
  * wait holds no lock; a thread whose frame has been overtaken by eight later REPORT_COUNT frames on the device gets SHERF_EINVAL instead of

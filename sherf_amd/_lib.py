@@ -77,6 +77,10 @@ class Frame(ctypes.Structure):                        # sherf_frame
     _fields_ = _frame_fields()
 
 
+class FieldQuery(ctypes.Structure):                   # sherf_field_query (sherf_query_field; six 8-byte fields, no padding)
+    _fields_ = [('points', _vp), ('dirs', _vp), ('n', _i64), ('rgb', _vp), ('sigma', _vp), ('mask', _vp)]
+
+
 _STRUCTS = (VoxLevel, SvoxLevelWs, SvoxLayer, SvoxPlan, Frame)
 
 

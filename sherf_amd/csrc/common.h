@@ -87,6 +87,22 @@ __device__ __forceinline__ float dist2_exact(float ax, float ay, float az, float
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// World -> SMPL frame (renderer.py:309-310), shared by the ray sampler (csrc/sample.hip) and the point sampler (csrc/field.hip) so that the two
+// produce the same bits: (v - Th) @ R, evaluated without contraction in the order ((a0*R0c + a1*R1c) + a2*R2c)
+__device__ __forceinline__ void to_smpl_frame(float x, float y, float z, const float* __restrict__ R,
+                                              const float* __restrict__ Th, float& ox, float& oy, float& oz) {
+    float a0 = __fsub_rn(x, Th[0]), a1 = __fsub_rn(y, Th[1]), a2 = __fsub_rn(z, Th[2]);
+    ox = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[0]), __fmul_rn(a1, R[3])), __fmul_rn(a2, R[6]));
+    oy = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[1]), __fmul_rn(a1, R[4])), __fmul_rn(a2, R[7]));
+    oz = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[2]), __fmul_rn(a1, R[5])), __fmul_rn(a2, R[8]));
+}
+__device__ __forceinline__ void rot_only(float x, float y, float z, const float* __restrict__ R, float& ox,
+                                         float& oy, float& oz) {
+    ox = __fadd_rn(__fadd_rn(__fmul_rn(x, R[0]), __fmul_rn(y, R[3])), __fmul_rn(z, R[6]));
+    oy = __fadd_rn(__fadd_rn(__fmul_rn(x, R[1]), __fmul_rn(y, R[4])), __fmul_rn(z, R[7]));
+    oz = __fadd_rn(__fadd_rn(__fmul_rn(x, R[2]), __fmul_rn(y, R[5])), __fmul_rn(z, R[8]));
+}
+
 // sin / cos of an angle `a` [rad] with the range reduction done right: the phase in revolutions is a two-term product with
 // 1 / (2 pi) = kHi + kLo (the fma recovers the rounding error of a * kHi exactly), v_fract keeps its fraction, v_sin / v_cos take
 // revolutions.  Phase error < 1e-8 revolutions for |a| <= 2^8, against 6e-8 * |a| / (2 pi) of a plain a * (1 / 2 pi).
@@ -203,6 +219,11 @@ __device__ __forceinline__ void nn_search_batched(const CellGrid& g, const int32
         }
     }
 }
+
+// scan_ws of the samplers (include/sherf_hip.h: int32[R + R / 1024 + 2] for R rays, or rows of 64 points): [R] chunk-local bases, [<= R / 1024 + 1] chunk sums,
+// the last word = the two-pass sampler's candidate count
+struct SherfScanWs { int32_t* base_local; int32_t* chunk_sum; int32_t* cand_count; };
+static inline SherfScanWs sherf_scan_ws(int32_t* ws, int R) { return {ws, ws + R, ws + R + R / 1024 + 1}; }
 
 // order-preserving float <-> int map for atomicMin/atomicMax on floats of any sign
 __device__ __forceinline__ int f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }

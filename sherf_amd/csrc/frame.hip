@@ -21,6 +21,13 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
                               int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
                               uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream,
                               int32_t* sticky);                                                                                 // sample.hip
+int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
+                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
+                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);                               // sample.hip
+int sherf_points_mask_nn_impl(const float* points, int64_t n, const float* Rg, const float* Th, const float* grid_hdr, const int32_t* cell_start,
+                              const float* cell_pts, const uint32_t* near_mask, int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt,
+                              int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
+                              const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky);                               // field.hip
 
 namespace {
 
@@ -127,8 +134,10 @@ extern "C" int sherf_frame_count(int32_t* nv_host) {
 
 // The frame's launches, enqueued one by one on the three streams (with g_frame_mu held).  sherf_render_frame below either calls this, or captures
 // what it enqueues into a hipGraph once and replays the graph from then on.
+// `q` (sherf_query_field; NULL for a frame): the same launches with the point sampler (csrc/field.hip) in the ray sampler's place, the warp reading one view
+// direction per point, and the scatter-back in the compositing's place; the descriptor's ray fields and image outputs are then not looked at.
 static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
-                                sherf_stream_t stream_side, sherf_stream_t stream_aux) {
+                                sherf_stream_t stream_side, sherf_stream_t stream_aux, const sherf_field_query* q = nullptr) {
     hipStream_t main = as_stream(stream_main), side = as_stream(stream_side);
     if (phase == 4) {                                                // the sampler alone: counters[0] = the frame's valid samples
         SHERF_CHECK_ARG(f->R > 0 && f->S > 0 && f->capacity > 0);
@@ -171,7 +180,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                 d.init = true;
             }
         }
-        SHERF_CHECK_ARG(f->R > 0 && f->S > 0 && f->capacity > 0 && f->vox_plan);
+        SHERF_CHECK_ARG((q || (f->R > 0 && f->S > 0)) && f->capacity > 0 && f->vox_plan);
         const int V = SHERF_V;
         {
             std::lock_guard<std::mutex> lk(g_mu);
@@ -252,6 +261,11 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         if (lists)
             SHERF_RUN(sherf_build_near_lists(f->grid_hdr, f->cell_pts, V, 0.05f, f->near_hdr, f->near_list, f->near_list_cap, f->near_mask, stream_main));
         SHERF_CAP_TRACE("sampler");
+        if (q)
+            SHERF_RUN(sherf_points_mask_nn_impl(q->points, q->n, f->Rg, f->Th, f->grid_hdr, f->cell_start, f->cell_pts, f->near_mask, f->capacity, f->counters,
+                                                f->ray_base, f->ray_cnt, f->cs_idx, f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr,
+                                                f->near_list, stream_main, f->sticky));
+        else
         SHERF_RUN(sherf_sample_mask_nn_impl(f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->Rg, f->Th, f->grid_hdr, f->cell_start,
                                        f->cell_pts, f->near_mask, f->capacity, f->counters, f->ray_base, f->ray_cnt, f->cs_idx,
                                        f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky));
@@ -291,6 +305,11 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             if (c < cap) cap = c;
         }
         SHERF_CAP_TRACE("warp");
+        if (q)          // cs_idx holds point indices: one direction per point
+            SHERF_RUN(sherf_warp_geom_impl(f->counters, f->cs_idx, f->cs_vid, f->cs_xs, q->dirs, 1, f->Rg, f->T2C, f->C2S, f->tverts,
+                                           f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, cap, f->geom,
+                                           f->cs_tvid, stream_main));
+        else
         SHERF_RUN(sherf_warp_geom(f->counters, f->cs_idx, f->cs_vid, f->cs_xs, f->ray_d, f->S, f->Rg, f->T2C, f->C2S, f->tverts,
                                   f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, cap, f->geom,
                                   f->cs_tvid, stream_main));
@@ -374,6 +393,9 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
     if (phase & 2) {
         // ---- a15-a16 ----
         SHERF_CAP_TRACE("compositing");
+        if (q)          // ---- renderer.py:364-368 materialised ----
+            SHERF_RUN(sherf_field_scatter(f->counters, f->ray_mask, f->ray_base, f->sample_out, q->n, tok_cap, q->rgb, q->sigma, q->mask, stream_main));
+        else
         SHERF_RUN(sherf_composite_compact_cap(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, f->ray_d, f->near, f->far,
                                               f->R, f->S, f->white_back, tok_cap, f->rgb, f->depth, f->acc, stream_main));
         SHERF_PROF(6, main);
@@ -459,8 +481,9 @@ extern "C" int sherf_frame_observation_stats(int64_t* stats_host, int32_t n) {
     return SHERF_OK;
 }
 
-extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
-                                  sherf_stream_t stream_side, sherf_stream_t stream_aux) {
+// what sherf_render_frame and sherf_query_field refuse alike, before anything is enqueued
+static int check_frame_call(const sherf_frame* f, int phase, const sherf_vox_level* levels, sherf_stream_t stream_main, sherf_stream_t stream_side,
+                            sherf_stream_t stream_aux) {
     SHERF_CHECK_ARG(f && levels && ((phase & 3) || phase == 4) && stream_side != stream_main && (!stream_aux || (stream_aux != stream_main && stream_aux != stream_side)));
     SHERF_CHECK_ARG((f->white_back & ~(SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS)) == 0);
     SHERF_CHECK_ARG(!(f->mlp_prec & SHERF_MLP_OSG_DECODER) || f->wstream);          // (the OSG weight block: include/sherf_hip.h)
@@ -470,6 +493,24 @@ extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_lev
         for (int i = 0; i < 3; ++i)
             SHERF_CHECK_ARG(levels[i].wp && levels[i].rows && levels[i].rows == f->vox_plan->fold_rows[i] && levels[i].D > 0 && levels[i].H > 0 && levels[i].W > 0);
     }
+    return SHERF_OK;
+}
+
+// The field query's driver: phases 1 + 2 of a frame with the point sampler and the scatter-back (render_frame_enqueue with `q`).  Always enqueued launch by
+// launch: a query is never captured as a graph (its descriptor changes with every chunk of points).
+extern "C" int sherf_query_field(const sherf_frame* f, const sherf_field_query* q, sherf_vox_level* levels, sherf_stream_t stream_main,
+                                 sherf_stream_t stream_side, sherf_stream_t stream_aux) {
+    SHERF_CHECK_ARG(q && q->points && q->dirs && q->rgb && q->sigma && q->mask && q->n > 0 && q->n < 2147483648LL);
+    SHERF_RUN(check_frame_call(f, 3, levels, stream_main, stream_side, stream_aux));
+    SHERF_CHECK_ARG(f->capacity > 0 && f->capacity >= q->n && f->vox_plan);         // (the sampler's buffers hold a record per point)
+    std::lock_guard<std::mutex> frame_lock(g_frame_mu);
+    ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
+    return render_frame_enqueue(f, 3, levels, stream_main, stream_side, stream_aux, q);
+}
+
+extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
+                                  sherf_stream_t stream_side, sherf_stream_t stream_aux) {
+    SHERF_RUN(check_frame_call(f, phase, levels, stream_main, stream_side, stream_aux));
     std::lock_guard<std::mutex> frame_lock(g_frame_mu);
     if (phase != 4 && (phase & 1)) ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
     if (g_graph_on < 0) {

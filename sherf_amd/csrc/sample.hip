@@ -16,21 +16,6 @@ constexpr float kThresh2 = (float)(0.05 * 0.05);   // renderer.py:318 (python fl
 // 1873 on tests/test_hipcpu_sampler_edges.py's `body`), so the builders of the sampler's inputs refuse one (SHERF_SHELL_RADIUS in include/sherf_hip.h).
 constexpr float kShellRadius = SHERF_SHELL_RADIUS;
 
-// (v - Th) @ R, evaluated without contraction in the order ((a0*R0c + a1*R1c) + a2*R2c)
-__device__ __forceinline__ void to_smpl_frame(float x, float y, float z, const float* __restrict__ R,
-                                              const float* __restrict__ Th, float& ox, float& oy, float& oz) {
-    float a0 = __fsub_rn(x, Th[0]), a1 = __fsub_rn(y, Th[1]), a2 = __fsub_rn(z, Th[2]);
-    ox = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[0]), __fmul_rn(a1, R[3])), __fmul_rn(a2, R[6]));
-    oy = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[1]), __fmul_rn(a1, R[4])), __fmul_rn(a2, R[7]));
-    oz = __fadd_rn(__fadd_rn(__fmul_rn(a0, R[2]), __fmul_rn(a1, R[5])), __fmul_rn(a2, R[8]));
-}
-__device__ __forceinline__ void rot_only(float x, float y, float z, const float* __restrict__ R, float& ox,
-                                         float& oy, float& oz) {
-    ox = __fadd_rn(__fadd_rn(__fmul_rn(x, R[0]), __fmul_rn(y, R[3])), __fmul_rn(z, R[6]));
-    oy = __fadd_rn(__fadd_rn(__fmul_rn(x, R[1]), __fmul_rn(y, R[4])), __fmul_rn(z, R[7]));
-    oz = __fadd_rn(__fadd_rn(__fmul_rn(x, R[2]), __fmul_rn(y, R[5])), __fmul_rn(z, R[8]));
-}
-
 // ---------------------------------------------------------------------------------------------
 // cell list: one block of 1024 threads (n <= 6890 points)
 // ---------------------------------------------------------------------------------------------
@@ -1073,7 +1058,8 @@ __global__ void __launch_bounds__(256) warp_geom_kernel(const int32_t* __restric
     const int vid = cs_vid[c];
     const float4 xs = cs_xs[c];
     float vx, vy, vz;
-    rot_only(ray_d[ray * 3], ray_d[ray * 3 + 1], ray_d[ray * 3 + 2], Rg, vx, vy, vz);   // renderer.py:310
+    const float* rd = ray_d + (size_t)ray * 3;                                          // (a point index of the field query can pass 2^31 / 3)
+    rot_only(rd[0], rd[1], rd[2], Rg, vx, vy, vz);                                      // renderer.py:310
     // (the 3 x 4 affine as three 16-byte loads: rows of 48 bytes are 16-byte aligned; twelve scalar loads were a third of this kernel's
     //  load instructions, and it is bound by those like the gather -- DESIGN section 5.2)
     const float4* P4 = reinterpret_cast<const float4*>(T2C) + (size_t)vid * 3;
@@ -1109,6 +1095,9 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
                               const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
                               int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
                               uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky);
+int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
+                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
+                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);
 
 extern "C" int sherf_build_cells(const float* verts, int n, const float* R, const float* Th, float cell_size,
                                  float* grid_hdr, int32_t* cell_start, float* cell_pts, int32_t* scratch,
@@ -1167,6 +1156,55 @@ extern "C" int sherf_sample_mask_nn(const float* ray_o, const float* ray_d, cons
                                      cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr);
 }
 
+// Pass 2 of the two-pass sampler and the first scan kernel, on the candidate list some pass 1 left in `cand_list` (records (x_s, dense index), index = row * S + k):
+// cand_mark_kernel's for rays, point_mark_kernel's (csrc/field.hip) for caller-supplied points laid out as rows of S = 64.  Validity bits land in ray_mask, vertex
+// ids in dense_vid, the rows' counts and chunk-local bases in ray_cnt / base_local / chunk_sum; scan_top_kernel and a compaction follow.
+template <int N>
+static void search_and_scan(hipStream_t st, int R, int S, const float* grid_hdr, const int32_t* cell_start, const float4* cp, const float4* cand_list, int64_t list_cap,
+                            const int32_t* cand_count, const int32_t* near_hdr, const uint16_t* near_list, int32_t* dense_vid, uint64_t* ray_mask, int32_t* ray_cnt,
+                            int32_t* base_local, int32_t* chunk_sum) {
+    // the search is a PERSISTENT grid (the candidate count is only known on the device), eight workgroups per CU.  Capping it at six
+    // (22 KiB of LDS padding, as sample_nn_kernel below is) to keep wave slots free for the encoder's launches on the other stream
+    // was measured and LOST: 1.346 -> 1.381 ms per frame (profiles/r03_bench_d_*.txt) -- the search simply ran longer.
+    unsigned long long* rm = reinterpret_cast<unsigned long long*>(ray_mask);
+    const bool lists = near_hdr && near_list && !(g_sherf_debug & 16384);      // debug bit 14: the cell walk, for A/B runs
+    // persistent workgroups per CU of the list search: SIX of the eight that fit -- the other two wave slots per SIMD go to the
+    // encoder's small dependent launches on the other stream, which the frame waits for just as long (MI355X, dense framing: 8 ->
+    // 1.751 ms, 6 -> 1.726, 4 -> 1.774, 3 -> 1.826 per frame; profiles/r04_call_m_*).  Debug bits 20-23 override for A/B runs.
+    const int search_wgs = ((g_sherf_debug >> 20) & 15) ? ((g_sherf_debug >> 20) & 15) : 6;
+    const bool tight = (sherf_experiment() & 32768) != 0;           // bit 15: ... held to 80 registers (six workgroups per CU; three spilled) instead of 87 (five)
+    const bool deep = (sherf_experiment() & 16384) != 0;            // SHERF_EXPERIMENT bit 14: the list search one pipeline stage deeper (round 6)
+    if (lists && deep && tight)
+        hipLaunchKernelGGL((cand_search_lists2_kernel<N, 6>), dim3(search_wgs * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S,
+                           grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);
+    else if (lists && deep)
+        hipLaunchKernelGGL((cand_search_lists2_kernel<N, 5>), dim3(min(search_wgs, 5) * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S,
+                           grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);
+    else if (lists)
+        hipLaunchKernelGGL(cand_search_lists_kernel<N>, dim3(search_wgs * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S,
+                           grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);
+    else
+        hipLaunchKernelGGL(cand_search_kernel<N>, dim3(8 * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S,
+                           grid_hdr, cell_start, cp, rm, dense_vid);
+    hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(cdiv(R, 1024)), dim3(1024), 0, st, ray_mask, R, ray_cnt, base_local, chunk_sum);
+}
+
+// The point sampler's use of this file's machinery (csrc/field.hip: sherf_points_mask_nn_impl; `rows` rows of 64 points).  _begin resets the counters and the
+// candidate count ahead of point_mark_kernel; _search runs the candidate search and both scan kernels behind it: counters[0] = the valid points.
+int sherf_points_begin_impl(int32_t* counters, int32_t* scan_ws, int rows, int32_t* sticky, sherf_stream_t stream) {
+    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream), counters, sherf_scan_ws(scan_ws, rows).cand_count, sticky);
+    SHERF_LAUNCH_CHECK();
+}
+int sherf_points_search_impl(int rows, const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const float* cand_list, int64_t list_cap,
+                             int32_t* counters, int32_t* ray_cnt, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
+                             const uint16_t* near_list, sherf_stream_t stream) {
+    const SherfScanWs w = sherf_scan_ws(scan_ws, rows);
+    search_and_scan<1>(as_stream(stream), rows, 64, grid_hdr, cell_start, reinterpret_cast<const float4*>(cell_pts), reinterpret_cast<const float4*>(cand_list),
+                       list_cap, w.cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, w.base_local, w.chunk_sum);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.chunk_sum, cdiv(rows, 1024), counters);
+    SHERF_LAUNCH_CHECK();
+}
+
 // (the frame driver's entry: `sticky`, see init_counters_kernel)
 int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const float* near, const float* far,
                               int R, int S, const float* Rg, const float* Th, const float* grid_hdr,
@@ -1180,45 +1218,24 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
     hipStream_t st = as_stream(stream);
     const int nch = (S + 63) / 64;
     const int n_chunks = cdiv(R, 1024);
-    int32_t* base_local = scan_ws;              // [R]
-    int32_t* chunk_sum = scan_ws + R;           // [n_chunks]
+    const SherfScanWs sw = sherf_scan_ws(scan_ws, R);
+    int32_t* base_local = sw.base_local;        // [R]
+    int32_t* chunk_sum = sw.chunk_sum;          // [n_chunks]
     const float4* cp = reinterpret_cast<const float4*>(cell_pts);
-    int32_t* cand_count = scan_ws + R + R / 1024 + 1;      // last word of scan_ws ([R] local bases, [<= R/1024 + 1] chunk sums, this)
+    int32_t* cand_count = sw.cand_count;
     hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, st, counters, cand_count, sticky);
     hipLaunchKernelGGL(depth_minmax_kernel, dim3(min(256, cdiv(R, 256))), dim3(256), 0, st, near, far, R, S, counters);
     // two passes over a dense candidate list (see cand_mark_kernel) whenever the list -- `capacity` records in cs_xs, which the
     // compaction below only writes afterwards -- provably holds every sample; sherf_set_debug bit 9 forces the one-wave-per-ray kernel
     const bool two_pass = !(g_sherf_debug & 512) && capacity >= (int64_t)R * S;
     if (two_pass) {
-        // the search is a PERSISTENT grid (the candidate count is only known on the device), eight workgroups per CU.  Capping it at six
-        // (22 KiB of LDS padding, as sample_nn_kernel below is) to keep wave slots free for the encoder's launches on the other stream
-        // was measured and LOST: 1.346 -> 1.381 ms per frame (profiles/r03_bench_d_*.txt) -- the search simply ran longer.
         float4* cand_list = reinterpret_cast<float4*>(cs_xs);            // one 16-byte record per candidate: the list holds `capacity` of them
         const int64_t list_cap = capacity;
-        unsigned long long* rm = reinterpret_cast<unsigned long long*>(ray_mask);
-        const bool lists = near_hdr && near_list && !(g_sherf_debug & 16384);      // debug bit 14: the cell walk, for A/B runs
-        // persistent workgroups per CU of the list search: SIX of the eight that fit -- the other two wave slots per SIMD go to the
-        // encoder's small dependent launches on the other stream, which the frame waits for just as long (MI355X, dense framing: 8 ->
-        // 1.751 ms, 6 -> 1.726, 4 -> 1.774, 3 -> 1.826 per frame; profiles/r04_call_m_*).  Debug bits 20-23 override for A/B runs.
-        const int search_wgs = ((g_sherf_debug >> 20) & 15) ? ((g_sherf_debug >> 20) & 15) : 6;
-        const bool tight = (sherf_experiment() & 32768) != 0;           // bit 15: ... held to 80 registers (six workgroups per CU; three spilled) instead of 87 (five)
-        const bool deep = (sherf_experiment() & 16384) != 0;            // SHERF_EXPERIMENT bit 14: the list search one pipeline stage deeper (round 6)
 #define SHERF_TWO_PASS(N)                                                                                                          \
         hipLaunchKernelGGL(cand_mark_kernel<N>, dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th,    \
                            grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug);                         \
-        if (lists && deep && tight)                                                                                                \
-            hipLaunchKernelGGL((cand_search_lists2_kernel<N, 6>), dim3(search_wgs * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S, \
-                               grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);                   \
-        else if (lists && deep)                                                                                                    \
-            hipLaunchKernelGGL((cand_search_lists2_kernel<N, 5>), dim3(min(search_wgs, 5) * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S, \
-                               grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);                   \
-        else if (lists)                                                                                                            \
-            hipLaunchKernelGGL(cand_search_lists_kernel<N>, dim3(search_wgs * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S, \
-                               grid_hdr, reinterpret_cast<const int2*>(near_hdr), near_list, cp, rm, dense_vid);                   \
-        else                                                                                                                       \
-            hipLaunchKernelGGL(cand_search_kernel<N>, dim3(8 * n_cus()), dim3(256), 0, st, cand_list, list_cap, cand_count, S,          \
-                               grid_hdr, cell_start, cp, rm, dense_vid);                                                           \
-        hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(n_chunks), dim3(1024), 0, st, ray_mask, R, ray_cnt, base_local, chunk_sum)
+        search_and_scan<N>(st, R, S, grid_hdr, cell_start, cp, cand_list, list_cap, cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, base_local, \
+                           chunk_sum)
         if (nch == 1) { SHERF_TWO_PASS(1); } else if (nch == 2) { SHERF_TWO_PASS(2); } else if (nch == 3) { SHERF_TWO_PASS(3); } else { SHERF_TWO_PASS(4); }
 #undef SHERF_TWO_PASS
     } else {
@@ -1265,9 +1282,18 @@ extern "C" int sherf_warp_geom(const int32_t* counters, const int32_t* cs_idx, c
                                const float* C2S, const float* t_verts, const float* tgrid_hdr,
                                const int32_t* tcell_start, const float* tcell_pts, int64_t capacity, float* geom,
                                int32_t* cs_tvid, sherf_stream_t stream) {
+    SHERF_CHECK_ARG(S >= 2);
+    return sherf_warp_geom_impl(counters, cs_idx, cs_vid, cs_xs, ray_d, S, Rg, T2C, C2S, t_verts, tgrid_hdr, tcell_start, tcell_pts, capacity, geom, cs_tvid, stream);
+}
+
+// `dir_stride`: how many consecutive dense indices share one row of `dirs` -- S for a frame's rays (the exported entry point, which refuses S < 2), 1 for the
+// field query's per-point view directions (csrc/frame.hip: dirs[cs_idx[c]]).  The kernel divides cs_idx by it either way.
+int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
+                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
+                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream) {
     SHERF_CHECK_ARG(counters && cs_idx && cs_vid && cs_xs && ray_d && Rg && T2C && C2S && t_verts && tgrid_hdr &&
                     tcell_start && tcell_pts && geom && cs_tvid);
-    SHERF_CHECK_ARG(S >= 2 && capacity > 0);
+    SHERF_CHECK_ARG(S >= 1 && capacity > 0);
     // (SHERF_EXPERIMENT bits 16-19, round 6: w persistent workgroups per CU instead of one per 256 samples -- room for the encoder's big-register waves beside it)
     const int warp_wgs = (sherf_experiment() >> 16) & 15;
     const int warp_grid = warp_wgs ? min(warp_wgs * n_cus(), cdiv(capacity, 256)) : min(8192, cdiv(capacity, 256));

@@ -398,7 +398,7 @@ class ImportanceRenderer(nn.Module):
 
     def __getstate__(self):
         s = self.__dict__.copy()
-        for k in ('_smpl_dev', '_ws', '_wcache', 'last', '_flags', '_frame_memo', '_pack_flag_pending'):
+        for k in ('_smpl_dev', '_ws', '_wcache', 'last', '_flags', '_frame_memo', '_pack_flag_pending', '_qws', 'last_query'):
             s[k] = None
         s['_ws'] = None
         return s
@@ -1061,6 +1061,82 @@ class ImportanceRenderer(nn.Module):
         st = self.__dict__.get('_obs_stats') or (0, 0)
         return int(st[0]), int(st[1])
 
+    def _describe(self, wsp, wc, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, input_data, opts, dev, keep):
+        """The part of the `sherf_frame` descriptor that does not depend on what is sampled -- SMPL parameter sets, cameras, vertices, the folded tables, the
+        gather's switches, the encoder plan and this call's voxels, the streams -- for `forward` (rays) and `query_points` (points) alike.
+        -> (descriptor, dict of what the callers go on with).  Only collects pointers; conversions that must outlive the enqueue go to `keep`."""
+        F32 = torch.float32
+
+        def f32(t):                                    # (already fp32 and contiguous -- the usual case: no dispatcher round trips)
+            return t if (t.dtype is F32 and t.is_contiguous() and not t.requires_grad) else t.detach().to(dtype=F32).contiguous()
+        smpl = self._smpl(dev)
+        prm, oprm, tprm = input_data['params'], input_data['obs_params'], input_data['t_params']
+        main = torch.cuda.current_stream(dev)
+        side = self._side(dev)
+        A = _lib.addr
+        fr = wsp.descriptor(smpl)                                        # workspace / asset pointers: filled in once per workspace
+
+        def a32(t, n):                                                   # address of `t` as n contiguous fp32 values
+            t = f32(t)
+            if t.numel() != n:
+                raise RuntimeError(f'sherf_amd: expected {n} values, got a tensor of shape {tuple(t.shape)}')
+            keep.append(t)
+            return A(t)
+
+        # the three SMPL parameter sets side by side (target, big pose, observation): two small concatenations per frame -- reused while
+        # the six source tensors are the same objects at the same versions (a static subject / camera sweep)
+        srcs = (prm['poses'], tprm['poses'], oprm['poses'], prm['shapes'], tprm['shapes'], oprm['shapes'])
+        skey = tuple([(id(t), t._version, t.data_ptr()) for t in srcs])
+        if wsp.stacked is None or wsp.stacked[0] != skey:
+            # (written into the SAME two tensors every time: their addresses are part of the frame graph's key, csrc/frame.hip)
+            old = wsp.stacked
+            po = old[1] if old is not None and old[1].device == dev else torch.empty(3, 72, dtype=F32, device=dev)
+            sh = old[2] if old is not None and old[2].device == dev else torch.empty(3, 10, dtype=F32, device=dev)
+            torch.stack([f32(t).reshape(72) for t in srcs[:3]], out=po)
+            torch.stack([f32(t).reshape(10) for t in srcs[3:]], out=sh)
+            wsp.stacked = (skey, po, sh, srcs)
+        poses, shapes = wsp.stacked[1], wsp.stacked[2]
+        fr.poses, fr.shapes = A(poses), A(shapes)
+        nl = wsp.desc[3]
+        if opts.get('near_lists', getattr(self, 'near_lists', True)):           # exact vertex list per near-mask sub-cell (False: the cell walk)
+            fr.near_hdr, fr.near_list, fr.near_list_cap = nl['near_hdr'], nl['near_list'], nl['near_cap']
+        else:
+            fr.near_hdr, fr.near_list, fr.near_list_cap = None, None, 0
+        fr.obs_R, fr.obs_Th = a32(oprm['R'], 9), a32(oprm['Th'], 3)
+        fr.cam_R, fr.cam_T, fr.cam_K = a32(input_data['obs_R_all'], 9), a32(input_data['obs_T_all'], 3), a32(input_data['obs_K_all'], 9)
+        fr.verts, fr.tverts = a32(input_data['vertices'], V * 3), a32(input_data['t_vertices'], V * 3)
+        fr.Rg, fr.Th = a32(prm['R'], 9), a32(prm['Th'], 3)
+        # per-frame table re-layout (channel-last) with the slot projections folded in
+        Pres = planes.shape[-1]
+        Hf, Wf = obs_input_feature.shape[-2:]
+        H, W = obs_input_img.shape[-2:]
+        planes_f = wsp.table('planes_f', (3, Pres, Pres, 32), dev)
+        feat_f = wsp.table('feat_f', (Hf, Wf, 64), dev)
+        img4 = wsp.table('img4', (H, W, 4), dev)
+        fr.planes, fr.Wa_t, fr.planes_f, fr.P = a32(planes, planes.numel()), A(wc['Wa_t']), A(planes_f), Pres
+        fr.obs_feat, fr.Wb_t, fr.feat_f, fr.Hf, fr.Wf = a32(obs_input_feature, obs_input_feature.numel()), A(wc['Wb_t']), A(feat_f), Hf, Wf
+        fr.obs_img, fr.img4, fr.H, fr.W = a32(obs_input_img, obs_input_img.numel()), A(img4), H, W
+        fr.tok_bias, fr.bounds = A(wc['tok_bias']), a32(input_data['t_world_bounds'], 6)
+        vox_min = f32(obs_sp_input['bounds'])                            # [.., 2, 3]: its first row = the voxel grid's origin
+        if vox_min.numel() != 6:
+            raise RuntimeError('sherf_amd: obs_sp_input["bounds"] must hold 2 x 3 values')
+        keep.append(vox_min)
+        fr.vox_min = A(vox_min)
+        for i, v in enumerate(obs_sp_input['out_sh']):
+            fr.vox_sh[i] = int(v)
+        gb = opts.get('gather_branchless', self.gather_branchless)
+        fr.gather_split = (1 if opts.get('gather_split', self.gather_split) else 0) | (4 if gb == '128' else 2 if gb else 0)
+        # a11: sparse voxel encoder plan (persistent buffers) + this frame's voxels
+        pl, vfeat, vcoord = self.encoder_3d.prepare(canonical_sp_conv_volume, wc['fold'], wsp)
+        keep += [vfeat, vcoord]
+        fr.vox_plan = _ct.addressof(pl['plan'])
+        fr.vox_coord, fr.vox_feat, fr.vox_n, fr.vox_training = A(vcoord), A(vfeat), vfeat.shape[0], 1 if self.encoder_3d.training else 0
+        levels = (_lib.VoxLevel * 3)()
+        s_main, s_side = _ct.c_void_p(main.cuda_stream), _ct.c_void_p(side.cuda_stream)
+        s_aux = _ct.c_void_p(self._side(dev, 1).cuda_stream) if opts.get('aux_stream', self.aux_stream) else None
+        return fr, dict(a32=a32, pl=pl, planes_f=planes_f, feat_f=feat_f, img4=img4, vox_min=vox_min, vcoord=vcoord, H=H, W=W, levels=levels,
+                        streams=(s_main, s_side, s_aux))
+
     # ---- forward -----------------------------------------------------------------------------
     def forward(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
                 decoder, ray_origins, ray_directions, near, far, input_data, rendering_options):
@@ -1119,11 +1195,6 @@ class ImportanceRenderer(nn.Module):
         S = int(opts['depth_resolution'])
         R = ray_origins.shape[1]
         cap = int(opts.get('sample_capacity', R * S))
-        F32 = torch.float32
-
-        def f32(t):                                    # (already fp32 and contiguous -- the usual case: no dispatcher round trips)
-            return t if (t.dtype is F32 and t.is_contiguous() and not t.requires_grad) else t.detach().to(dtype=F32).contiguous()
-        smpl = self._smpl(dev)
         clamp_mode = opts.get('clamp_mode', 'relu')
         self.__dict__['_clamp_mode'] = clamp_mode                        # (part of what an `auto` choice was measured under: _auto_state_key)
         cfg, calibrate = self._resolve_config(opts, decoder, dev)
@@ -1134,44 +1205,17 @@ class ImportanceRenderer(nn.Module):
         wc = self._weights(decoder, dev, prec_name)
         wsp = self._workspace(dev)
         ws = wsp.frame(R, S, cap, dev)
-        prm, oprm, tprm = input_data['params'], input_data['obs_params'], input_data['t_params']
-
+        prm = input_data['params']
         # One native call enqueues the whole frame on two HIP streams (csrc/frame.hip): the sparse voxel encoder is a chain
         # of ~35 small launches that cannot fill the chip and is independent of the ray side of the frame until the
         # gather -> it runs (with the SMPL tables) on a side stream, concurrently with cell lists / sampling / compaction /
         # table folding on the caller's stream.  Everything below only collects pointers.
-        main = torch.cuda.current_stream(dev)
-        side = self._side(dev)
         A = _lib.addr
-        fr = wsp.descriptor(smpl)                                        # workspace / asset pointers: filled in once per workspace
         keep = []                                                        # conversions that must outlive the enqueue
-
-        def a32(t, n):                                                   # address of `t` as n contiguous fp32 values
-            t = f32(t)
-            if t.numel() != n:
-                raise RuntimeError(f'sherf_amd: expected {n} values, got a tensor of shape {tuple(t.shape)}')
-            keep.append(t)
-            return A(t)
-
-        # the three SMPL parameter sets side by side (target, big pose, observation): two small concatenations per frame -- reused while
-        # the six source tensors are the same objects at the same versions (a static subject / camera sweep)
-        srcs = (prm['poses'], tprm['poses'], oprm['poses'], prm['shapes'], tprm['shapes'], oprm['shapes'])
-        skey = tuple([(id(t), t._version, t.data_ptr()) for t in srcs])
-        if wsp.stacked is None or wsp.stacked[0] != skey:
-            # (written into the SAME two tensors every time: their addresses are part of the frame graph's key, csrc/frame.hip)
-            old = wsp.stacked
-            po = old[1] if old is not None and old[1].device == dev else torch.empty(3, 72, dtype=F32, device=dev)
-            sh = old[2] if old is not None and old[2].device == dev else torch.empty(3, 10, dtype=F32, device=dev)
-            torch.stack([f32(t).reshape(72) for t in srcs[:3]], out=po)
-            torch.stack([f32(t).reshape(10) for t in srcs[3:]], out=sh)
-            wsp.stacked = (skey, po, sh, srcs)
-        poses, shapes = wsp.stacked[1], wsp.stacked[2]
-        fr.poses, fr.shapes = A(poses), A(shapes)
-        nl = wsp.desc[3]
-        if opts.get('near_lists', getattr(self, 'near_lists', True)):           # exact vertex list per near-mask sub-cell (False: the cell walk)
-            fr.near_hdr, fr.near_list, fr.near_list_cap = nl['near_hdr'], nl['near_list'], nl['near_cap']
-        else:
-            fr.near_hdr, fr.near_list, fr.near_list_cap = None, None, 0
+        fr, ob = self._describe(wsp, wc, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, input_data, opts, dev, keep)
+        a32 = ob['a32']
+        pl, planes_f, feat_f, img4, vox_min, vcoord, H, W = ob['pl'], ob['planes_f'], ob['feat_f'], ob['img4'], ob['vox_min'], ob['vcoord'], ob['H'], ob['W']
+        levels, (s_main, s_side, s_aux) = ob['levels'], ob['streams']
         # the frame's outputs: ONE fresh buffer per call, planar [rgb (3R) | depth (R) | acc (R)], written by the compositing kernel and
         # returned as views -- no copies behind the frame (rounds 1-2 cloned three workspace tensors: three launches per frame), and
         # a caller may keep as many frames as it likes
@@ -1186,42 +1230,10 @@ class ImportanceRenderer(nn.Module):
         else:
             out = torch.empty(5 * R, dtype=torch.float32, device=dev)
         fr.rgb, fr.depth, fr.acc = A(out), A(out) + 12 * R, A(out) + 16 * R
-        fr.obs_R, fr.obs_Th = a32(oprm['R'], 9), a32(oprm['Th'], 3)
-        fr.cam_R, fr.cam_T, fr.cam_K = a32(input_data['obs_R_all'], 9), a32(input_data['obs_T_all'], 3), a32(input_data['obs_K_all'], 9)
-        fr.verts, fr.tverts = a32(input_data['vertices'], V * 3), a32(input_data['t_vertices'], V * 3)
-        fr.Rg, fr.Th = a32(prm['R'], 9), a32(prm['Th'], 3)
         fr.ray_o, fr.ray_d = a32(ray_origins, R * 3), a32(ray_directions, R * 3)
         fr.near, fr.far = a32(near, R), a32(far, R)
         fr.R, fr.S, fr.capacity = R, S, cap
-        # per-frame table re-layout (channel-last) with the slot projections folded in
-        Pres = planes.shape[-1]
-        Hf, Wf = obs_input_feature.shape[-2:]
-        H, W = obs_input_img.shape[-2:]
-        planes_f = wsp.table('planes_f', (3, Pres, Pres, 32), dev)
-        feat_f = wsp.table('feat_f', (Hf, Wf, 64), dev)
-        img4 = wsp.table('img4', (H, W, 4), dev)
-        fr.planes, fr.Wa_t, fr.planes_f, fr.P = a32(planes, planes.numel()), A(wc['Wa_t']), A(planes_f), Pres
         exact = bool(opts.get('exact_grids', self.exact_grids))
-        fr.obs_feat, fr.Wb_t, fr.feat_f, fr.Hf, fr.Wf = a32(obs_input_feature, obs_input_feature.numel()), A(wc['Wb_t']), A(feat_f), Hf, Wf
-        fr.obs_img, fr.img4, fr.H, fr.W = a32(obs_input_img, obs_input_img.numel()), A(img4), H, W
-        fr.tok_bias, fr.bounds = A(wc['tok_bias']), a32(input_data['t_world_bounds'], 6)
-        vox_min = f32(obs_sp_input['bounds'])                            # [.., 2, 3]: its first row = the voxel grid's origin
-        if vox_min.numel() != 6:
-            raise RuntimeError('sherf_amd: obs_sp_input["bounds"] must hold 2 x 3 values')
-        keep.append(vox_min)
-        fr.vox_min = A(vox_min)
-        for i, v in enumerate(obs_sp_input['out_sh']):
-            fr.vox_sh[i] = int(v)
-        gb = opts.get('gather_branchless', self.gather_branchless)
-        fr.gather_split = (1 if opts.get('gather_split', self.gather_split) else 0) | (4 if gb == '128' else 2 if gb else 0)
-        # a11: sparse voxel encoder plan (persistent buffers) + this frame's voxels
-        pl, vfeat, vcoord = self.encoder_3d.prepare(canonical_sp_conv_volume, wc['fold'], wsp)
-        keep += [vfeat, vcoord]
-        fr.vox_plan = _ct.addressof(pl['plan'])
-        fr.vox_coord, fr.vox_feat, fr.vox_n, fr.vox_training = A(vcoord), A(vfeat), vfeat.shape[0], 1 if self.encoder_3d.training else 0
-        levels = (_lib.VoxLevel * 3)()
-        s_main, s_side = _ct.c_void_p(main.cuda_stream), _ct.c_void_p(side.cuda_stream)
-        s_aux = _ct.c_void_p(self._side(dev, 1).cuda_stream) if opts.get('aux_stream', self.aux_stream) else None
 
         # token-side workspace: sized from the frame's own count (see _token_capacity)
         def probe():
@@ -1343,3 +1355,134 @@ class ImportanceRenderer(nn.Module):
         self.last['observation_reused'] = reused
         return ws['rgb'].view(1, R, 3), ws['depth'].view(1, R, 1), ws['acc'].view(1, R, 1)
 
+
+    # ---- field query ---------------------------------------------------------------------------------------------------------------
+    def _query_workspace(self, dev):
+        """The query's own workspace per (device, caller stream): a query lays its points out as rows of 64 and sizes the sampler's buffers for them, which on the
+        frames' workspace would re-size it and drop what it holds for the next frame -- its token capacity, the observation a sweep reuses, `last`."""
+        q = self.__dict__.get('_qws')
+        if not isinstance(q, dict):
+            q = self.__dict__['_qws'] = {}
+        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+        w = q.pop(key, None)
+        if w is None:
+            w = _Workspace()
+            while len(q) >= self.MAX_WORKSPACES:
+                if dev.type == 'cuda' and torch.cuda.is_available():
+                    torch.cuda.synchronize(dev)
+                del q[next(iter(q))]
+        q[key] = w
+        return w
+
+    def _query_config(self, opts, decoder, dev):
+        """forward's precision resolution without its calibration: mlp_precision='auto' takes the choice already calibrated for these weights by a frame, else the
+        fp32-grade reference configuration; the choice's frame count and re-check schedule are left alone."""
+        mlp = opts.get('mlp_precision') or self.mlp_precision
+        if mlp != 'auto' or not self.use_NeRF_decoder:
+            return self._resolve_config(opts, decoder, dev)[0]
+        self._weights(decoder, dev, 'f16x3')
+        choice = self._wcache.get('auto') or self.REFERENCE_CONFIG
+        tab = opts.get('table_precision') or getattr(self, 'table_precision', 'auto')
+        enc = opts.get('encoder_precision') or getattr(self, 'encoder_precision', 'auto')
+        return (choice[0], choice[1] if tab == 'auto' else tab, choice[2] if enc == 'auto' else enc)
+
+    def query_stats(self):
+        """Counters of this renderer's field queries: chunks issued, chunks that encoded / reused the observation, token-buffer re-sizes."""
+        return dict(self.__dict__.get('_query_stats') or dict(chunks=0, encoded=0, reused=0, resizes=0))
+
+    def query_points(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
+                     decoder, points, directions, input_data, rendering_options):
+        """Density and colour of the field at arbitrary points: `forward` from the SMPL-frame transform to the scatter-back (the reference's renderer.py:307-368)
+        with `points` / `directions` [1, N, 3] -- world frame, as ray_origins / ray_directions -- in place of the ray samples and their directions; what the
+        reference declares as TriPlaneGenerator.sample (triplane.py:219-230).  -> dict(rgb [1, N, 3], sigma [1, N, 1] (raw, before the clamp mode's
+        activation), mask [1, N] bool: within 5 cm of a posed vertex); rgb 0 / sigma -80 where the mask fails, as colors_coarse / densities_coarse there.
+        Inference only (no gradient is recorded); `density_noise` is ignored.  Same weights cache, precision resolution and launch form as `forward`
+        (mlp_precision='auto': the calibrated choice if a frame has made one, else f16x3 -- a query never calibrates).  rendering_options['query_chunk']
+        (default 2^24, rounded down to a multiple of 64) points go through one native call (csrc/frame.hip: sherf_query_field); the first chunk encodes the
+        observation, the others reuse it.  The token buffers grow to each chunk's own count of valid points: a query never returns the overflow NaN."""
+        self._check_decoder(decoder)
+        if not points.is_cuda:
+            raise RuntimeError('sherf_amd.ImportanceRenderer runs on the GPU only (no CPU fallback)')
+        if points.shape[0] != 1:
+            raise RuntimeError('per-GPU batch must be 1, as in the reference (renderer.py:320-321,567)')
+        if points.ndim != 3 or points.shape[-1] != 3 or tuple(directions.shape) != tuple(points.shape) or points.shape[1] < 1:
+            raise ValueError(f'points and directions must both be [1, N, 3] with N >= 1, got {tuple(points.shape)} and {tuple(directions.shape)}')
+        if points.device.index is not None and points.device.index != torch.cuda.current_device():
+            with torch.cuda.device(points.device):
+                return self.query_points(planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
+                                         decoder, points, directions, input_data, rendering_options)
+        d, enc = self.__dict__, self.encoder_3d.__dict__
+        memo, kmemo = d.get('_frame_memo'), enc.get('_key_memo')
+        d['_frame_memo'] = (None, None, None)
+        enc['_key_memo'] = state_key(fast_params(self.encoder_3d))
+        try:
+            with torch.no_grad():
+                return self._query(planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, decoder, points, directions,
+                                   input_data, rendering_options)
+        finally:
+            d['_frame_memo'], enc['_key_memo'] = memo, kmemo
+
+    def _query(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, decoder, points, directions, input_data, opts):
+        dev = points.device
+        N = int(points.shape[1])
+        chunk = max(64, int(opts.get('query_chunk', 1 << 24)) // 64 * 64)
+        rows = (min(N, chunk) + 63) // 64
+        cap = rows * 64                                                  # the sampler's buffers: a record per point of the largest chunk
+        cfg = self._query_config(opts, decoder, dev)
+        d = self.__dict__
+        d['_opt_mlp_split'], d['_opt_pe_in_gather'] = False, False       # (opt-in forms with scratch in the frames' workspace: not for a query)
+        d['_opt_mlp_form'] = opts.get('mlp_form')
+        d['_opt_report_count'] = True                                    # every chunk reports its count behind the sampler
+        wc = self._weights(decoder, dev, cfg[0])
+        wsp = self._query_workspace(dev)
+        ws = wsp.frame(rows, 64, cap, dev)
+        keep = []
+        fr, ob = self._describe(wsp, wc, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, input_data, opts, dev, keep)
+        a32, levels, streams = ob['a32'], ob['levels'], ob['streams']
+        fr.R, fr.S, fr.capacity = rows, 64, cap
+        fr.white_back = 0
+        want = opts.get('token_capacity', getattr(self, 'token_capacity', 'auto'))
+        tok = cap if want in ('worst', None) else wsp.tok_cap if want == 'auto' else self._round_tokens(int(want), cap)
+        if tok != wsp.tok_cap:
+            if dev.type == 'cuda' and ws['counters'].device.type == 'cuda':
+                torch.cuda.synchronize(dev)                              # queries in flight still read the old buffers
+            wsp.tokens(tok, dev)
+        fr.tok_capacity = wsp.tok_cap
+        self._set_config(fr, decoder, dev, cfg, bool(opts.get('exact_grids', self.exact_grids)))
+        fr.mlp_parts = int(opts.get('mlp_parts', getattr(self, 'mlp_parts', 0)))
+        fr.main_after_layer = int(opts.get('main_after_layer', self.main_after_layer))
+        A = _lib.addr
+        p_pts, p_dirs = a32(points, N * 3), a32(directions, N * 3)
+        rgb = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        sigma = torch.empty(N, dtype=torch.float32, device=dev)
+        mask = torch.empty(N, dtype=torch.uint8, device=dev)
+        st = d.setdefault('_query_stats', dict(chunks=0, encoded=0, reused=0, resizes=0))
+        q = _lib.FieldQuery()
+        base_flags = int(fr.flags) & ~_lib.FRAME_REUSE_OBSERVATION
+        counts, encoded = [], False
+        for off in range(0, N, chunk):
+            n = min(chunk, N - off)
+            q.points, q.dirs, q.n = p_pts + 12 * off, p_dirs + 12 * off, n
+            q.rgb, q.sigma, q.mask = A(rgb) + 12 * off, A(sigma) + 4 * off, A(mask) + off
+            while True:
+                # the first native call of this query encodes the observation; every later one -- the other chunks, a chunk issued again on larger token
+                # buffers -- renders from what it left in this workspace (same inputs by construction: no key needed)
+                fr.flags = base_flags | (_lib.FRAME_REUSE_OBSERVATION if encoded else 0)
+                _lib.call('sherf_query_field', _ct.byref(fr), _ct.byref(q), levels, *streams)
+                st['chunks'] += 1
+                st['reused' if encoded else 'encoded'] += 1
+                encoded = True
+                nv = _ct.c_int32(0)
+                _lib.call('sherf_frame_count', _ct.byref(nv))            # waits for this chunk's sampler only
+                if nv.value <= wsp.tok_cap:
+                    break
+                if dev.type == 'cuda' and ws['counters'].device.type == 'cuda':
+                    torch.cuda.synchronize(dev)
+                wsp.tokens(self._round_tokens(nv.value, cap), dev)       # this chunk's own count: nothing to guess
+                fr.tok_capacity = wsp.tok_cap
+                st['resizes'] += 1
+            counts.append(int(nv.value))
+        wsp.obs_key = None                                               # (this workspace never takes part in the frames' reuse)
+        d['last_query'] = dict(ws=ws, N=N, chunk=chunk, counts=counts, cap=wsp.tok_cap, keep=keep, mlp_precision=cfg[0], table_precision=cfg[1],
+                               encoder_precision=cfg[2], mlp_form=('pipelined' if fr.flags & 64 else 'two_tiles' if fr.flags & 32 else 'one'))
+        return dict(rgb=rgb.view(1, N, 3), sigma=sigma.view(1, N, 1), mask=mask.view(1, N).bool())

@@ -357,16 +357,9 @@ class TriPlaneGenerator(nn.Module):
             return None
         return oc
 
-    def synthesis(self, ws, input_data, c, neural_rendering_resolution=None, use_sr_module=True, update_emas=False,
-                  cache_backbone=False, use_cached_backbone=False, test_flag=False, planes=None, cache_observation=False,
-                  use_cached_observation=False, **synthesis_kwargs):
-        if neural_rendering_resolution is None:
-            neural_rendering_resolution = self.neural_rendering_resolution
-        else:
-            self.neural_rendering_resolution = neural_rendering_resolution
-        ray_origins, ray_directions = input_data['ray_o_all'][:, 0], input_data['ray_d_all'][:, 0]
-        near, far = input_data['near_all'][:, 0], input_data['far_all'][:, 0]
-        N, M, _ = ray_origins.shape
+    def _observation(self, ws, input_data, update_emas, cache_backbone, use_cached_backbone, planes, cache_observation, use_cached_observation, synthesis_kwargs):
+        """The producers of a frame (triplane.py:96-137), shared by `synthesis` and `sample_mixed`: tri-planes, observation feature map, vertex features and
+        mask, canonical observed vertices, voxelisation -> (planes [N,3,32,P,P], obs_input_img, obs_input_feature, sp, mask, sp_input, caching?)."""
         # cache_observation / use_cached_observation (beside and independent of cache_backbone / use_cached_backbone): everything below that depends
         # on the observation alone -- planes, feature map, vertex features and mask, canonical observed vertices, voxelisation -- is kept as the very
         # tensor objects the renderer saw, so that its own observation key matches and the frame renders from the tables and voxel levels already in
@@ -406,6 +399,20 @@ class TriPlaneGenerator(nn.Module):
                 self.__dict__['_obs_cache'] = dict(key=key, refs=key_refs, ws=ws, planes_arg=planes_arg, planes_raw=planes_raw, planes=planes, obs_input_img=obs_input_img,
                                                    obs_input_feature=obs_input_feature, vertex_features=f3d, mask=mask, canonical_obs_vertices=can,
                                                    sp_input=sp_input, sp=sp)
+        return planes, obs_input_img, obs_input_feature, sp, mask, sp_input, caching
+
+    def synthesis(self, ws, input_data, c, neural_rendering_resolution=None, use_sr_module=True, update_emas=False,
+                  cache_backbone=False, use_cached_backbone=False, test_flag=False, planes=None, cache_observation=False,
+                  use_cached_observation=False, **synthesis_kwargs):
+        if neural_rendering_resolution is None:
+            neural_rendering_resolution = self.neural_rendering_resolution
+        else:
+            self.neural_rendering_resolution = neural_rendering_resolution
+        ray_origins, ray_directions = input_data['ray_o_all'][:, 0], input_data['ray_d_all'][:, 0]
+        near, far = input_data['near_all'][:, 0], input_data['far_all'][:, 0]
+        N, M, _ = ray_origins.shape
+        planes, obs_input_img, obs_input_feature, sp, mask, sp_input, caching = self._observation(
+            ws, input_data, update_emas, cache_backbone, use_cached_backbone, planes, cache_observation, use_cached_observation, synthesis_kwargs)
         if test_flag:
             self.rendering_kwargs.update({'density_noise': 0})
         opts = self.rendering_kwargs
@@ -459,3 +466,28 @@ class TriPlaneGenerator(nn.Module):
         if oc is not None and oc['ws'] is ws:
             oc['mapping_call'], oc['c'] = mapping_call, (c if c_counts else None)
         return out
+
+    # ---- triplane.py:219-230: the field at arbitrary points ------------------------------------------------------------------
+    def sample(self, coordinates, directions, z, c, input_data=None, truncation_psi=1, truncation_cutoff=None, update_emas=False,
+               cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
+        """triplane.py:219-224 ("Compute RGB features, density for arbitrary 3D coordinates. Mostly used for extracting shapes"): the mapping network on
+        (z, c), then `sample_mixed`.  `input_data` is ours: the field is conditioned on the observation and the poses (the reference's method is stale --
+        it calls run_model with five of its nine arguments and skips the SMPL warp)."""
+        if input_data is None:
+            raise TypeError('sample() needs input_data: the field is conditioned on the observation view and the SMPL poses')
+        ws = self.mapping(z, c, input_img=input_data['obs_img_all'][:, 0], truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff,
+                          update_emas=update_emas)
+        return self.sample_mixed(coordinates, directions, ws, input_data=input_data, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff,
+                                 update_emas=update_emas, cache_backbone=cache_backbone, use_cached_backbone=use_cached_backbone, **synthesis_kwargs)
+
+    def sample_mixed(self, coordinates, directions, ws, input_data=None, truncation_psi=1, truncation_cutoff=None, update_emas=False,
+                     cache_backbone=False, use_cached_backbone=False, planes=None, **synthesis_kwargs):
+        """triplane.py:226-230 for given `ws`: the producers exactly as `synthesis` runs them (`planes`: as there, tri-planes to use instead of the
+        backbone's), then ImportanceRenderer.query_points on `coordinates` / `directions` [1, N, 3] (world frame)
+        -> {'rgb' [1, N, 3], 'sigma' [1, N, 1], 'mask' [1, N] bool}."""
+        if input_data is None:
+            raise TypeError('sample_mixed() needs input_data: the field is conditioned on the observation view and the SMPL poses')
+        planes, obs_input_img, obs_input_feature, sp, mask, sp_input, _ = self._observation(
+            ws, input_data, update_emas, cache_backbone, use_cached_backbone, planes, False, False, synthesis_kwargs)
+        return self.renderer.query_points(planes, obs_input_img, obs_input_feature, sp, mask, sp_input, self.decoder, coordinates, directions,
+                                          input_data, self.rendering_kwargs)
