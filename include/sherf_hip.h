@@ -125,6 +125,20 @@ int sherf_sample_mask_nn(const float* ray_o, const float* ray_d, const float* ne
                          int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
                          int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
                          int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream);
+/* The same with the workspace of the candidate search BY SUB-CELL: the two-pass sampler then groups its candidates by near-mask sub-cell and a wave
+ * tests up to 64 candidates of one sub-cell against the sub-cell's near list, read once -- instead of every candidate reading its whole list.  Same
+ * comparisons, bit-identical outputs.  cell_ws: int32[cell_ws_len], cell_ws_len >= SHERF_CELL_WS_INTS(R, S), 8-byte aligned (else SHERF_EINVAL); its
+ * first SHERF_NEAR_SUBCELLS words (the per-sub-cell counts) must be ZERO at the first call and are left zero by every call: allocate it zeroed, then
+ * only hand it over.  cs_idx / cs_vid hold the candidates in arrival order until the compaction writes them.  Taken when the near lists are given
+ * and capacity >= R * S; cell_ws == NULL, or sherf_set_debug bit 28 (A/B runs), is sherf_sample_mask_nn. */
+#define SHERF_CELL_WS_INTS(R, S) (4 * (int64_t)SHERF_NEAR_SUBCELLS + 6 + 2 * ((int64_t)(R) * (S) / 64))
+int sherf_sample_mask_nn_ws(const float* ray_o, const float* ray_d, const float* near, const float* far,
+                            int R, int S, const float* Rg, const float* Th, const float* grid_hdr,
+                            const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask,
+                            int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
+                            int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
+                            int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, int32_t* cell_ws, int64_t cell_ws_len,
+                            sherf_stream_t stream);
 
 /* a8+a9+a10 (geometry part): per compact sample: x_c, v_c via T2C[vid]; nearest T-pose vertex (exact, cell
  * list of t_vertices, renderer.py:627); uv via C2S.  geom[c][8] = (x_c.xyz, v_c.xyz, u, v); cs_tvid[c]. */
@@ -516,6 +530,7 @@ typedef struct {
     int32_t* sticky;            /* optional [3] (round 6): before a frame resets `counters` it folds what the previous frame left there into sticky[0] = max valid-sample
                                  * count, sticky[1] = OR of the flag words (counters[3]), sticky[2] += 1 -- a caller may then read its frames' flags every few
                                  * frames (one 32-byte copy + an event cost the caller's stream ~15 us per frame on the MI355X) instead of after every frame */
+    int32_t* cell_ws; int64_t cell_ws_len;   /* optional: the workspace of sherf_sample_mask_nn_ws (NULL: the candidate search by candidate) */
 } sherf_frame;
 int sherf_render_frame(const sherf_frame* frame, int phase, sherf_vox_level* levels_out_host, sherf_stream_t stream_main,
                        sherf_stream_t stream_side, sherf_stream_t stream_aux);

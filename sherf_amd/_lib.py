@@ -70,6 +70,8 @@ def _frame_fields():
     f.append(('tok_capacity', _i64))
     P('pefrag')
     P('sticky')
+    P('cell_ws')
+    f.append(('cell_ws_len', _i64))
     return f
 
 

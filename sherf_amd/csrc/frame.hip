@@ -20,7 +20,7 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
                               const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
                               int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
                               uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream,
-                              int32_t* sticky);                                                                                 // sample.hip
+                              int32_t* sticky, int32_t* cell_ws, int64_t cell_ws_len);                                          // sample.hip
 int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
                          const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
                          int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);                               // sample.hip
@@ -148,7 +148,8 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             SHERF_RUN(sherf_build_near_lists(f->grid_hdr, f->cell_pts, SHERF_V, 0.05f, f->near_hdr, f->near_list, f->near_list_cap, f->near_mask, stream_main));
         SHERF_RUN(sherf_sample_mask_nn_impl(f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->Rg, f->Th, f->grid_hdr, f->cell_start,
                                        f->cell_pts, f->near_mask, f->capacity, f->counters, f->ray_base, f->ray_cnt, f->cs_idx,
-                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky));
+                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky,
+                                       f->cell_ws, f->cell_ws_len));
         return SHERF_OK;
     }
     // token-side capacity: what geom / tokens / extras / sample_out hold
@@ -268,7 +269,8 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         else
         SHERF_RUN(sherf_sample_mask_nn_impl(f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->Rg, f->Th, f->grid_hdr, f->cell_start,
                                        f->cell_pts, f->near_mask, f->capacity, f->counters, f->ray_base, f->ray_cnt, f->cs_idx,
-                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky));
+                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky,
+                                       f->cell_ws, f->cell_ws_len));
         SHERF_CAP_TRACE("sampler queued");
         // SHERF_FRAME_EXACT_GRIDS: the kernels after the compaction are launched for the frame's ACTUAL number of valid samples instead
         // of the buffers' capacity (R*S, of which a body fills a few percent: the MLP's grid is then ~96 % workgroups that allocate

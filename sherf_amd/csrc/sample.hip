@@ -15,6 +15,11 @@ constexpr float kThresh2 = (float)(0.05 * 0.05);   // renderer.py:318 (python fl
 // vertex), which holds every vertex of the shell only on cells of at least that edge.  A finer grid gave a fraction of the valid samples without a word (0.02: 815 of
 // 1873 on tests/test_hipcpu_sampler_edges.py's `body`), so the builders of the sampler's inputs refuse one (SHERF_SHELL_RADIUS in include/sherf_hip.h).
 constexpr float kShellRadius = SHERF_SHELL_RADIUS;
+constexpr int kDebugSearchByCandidate = 1 << 28;   // sherf_set_debug bit 28: cand_search_lists_kernel where cand_search_cells_kernel would run (A/B runs)
+// persistent workgroups per CU of cand_search_cells_kernel.  MI355X, dense framing, whole frames interleaved in one process: 2 -> 1.508, 3 -> 1.507, 4 -> 1.508,
+// 5 -> 1.509, 6 -> 1.517, 8 -> 1.521 ms (the search by candidate at its six: 1.561; profiles/cells_search_wgs_sweep.txt) -- the fewer wave slots it takes from
+// the encoder's chain beside it the better, down to where it becomes the longer of the two
+constexpr int kCellSearchWgs = 4;
 
 // ---------------------------------------------------------------------------------------------
 // cell list: one block of 1024 threads (n <= 6890 points)
@@ -436,14 +441,20 @@ __global__ void __launch_bounds__(256) sample_nn_kernel(const float* __restrict_
 // (capacity >= R S, the default workspace).
 // ---------------------------------------------------------------------------------------------
 constexpr int kMarkRays = 4;          // rays in flight per wave of pass 1
+constexpr int kCellStage = 2048;      // CELLS: (dense index, rank) pairs a workgroup stages in the same 16 KiB; the rest goes out wave by wave
 
-template <int NCH>
+// CELLS (the search by sub-cell, cand_search_cells_kernel): pass 1 also COUNTS the candidates of every sub-cell -- a candidate's rank inside its
+// sub-cell is what a returning atomic on sub_cnt[q] gives it, one atomic per distinct sub-cell among the four rays a lane has in flight (neighbouring
+// rays share a sub-cell at the same depth index) -- and appends (dense index, rank) in arrival order to arr_idx / arr_rank (cs_idx / cs_vid: free until the
+// compaction) instead of the records, which cand_place_kernel evaluates once every sub-cell has its offset.
+template <int NCH, bool CELLS>
 __global__ void __launch_bounds__(256) cand_mark_kernel(const float* __restrict__ ray_o, const float* __restrict__ ray_d,
                                                         const float* __restrict__ near, const float* __restrict__ far, int R, int S,
                                                         const float* __restrict__ Rg, const float* __restrict__ Th,
                                                         const float* __restrict__ hdr, const uint32_t* __restrict__ near_mask,
                                                         float4* __restrict__ cand_list, int64_t list_cap, int32_t* __restrict__ cand_count,
-                                                        uint64_t* __restrict__ ray_mask, int dbg) {
+                                                        uint64_t* __restrict__ ray_mask, int dbg, int32_t* __restrict__ sub_cnt,
+                                                        int32_t* __restrict__ arr_idx, int32_t* __restrict__ arr_rank) {
     constexpr int RPW = 16 / NCH;                    // rays per wave: a workgroup stages at most 4 * RPW * 64 * NCH = 4096 candidates
     __shared__ int s_list[4096];
     __shared__ int s_n, s_base;
@@ -466,10 +477,10 @@ __global__ void __launch_bounds__(256) cand_mark_kernel(const float* __restrict_
         for (int ch = 0; ch < NCH; ++ch) {
             const int k = ch * 64 + lane;
             uint32_t word[kMarkRays];
-            int bit[kMarkRays];
+            int bit[kMarkRays], qs[kMarkRays];
 #pragma unroll
             for (int u = 0; u < kMarkRays; ++u) {      // every ray's mask word is requested before the first one is looked at
-                bit[u] = -1; word[u] = 0u;
+                bit[u] = -1; word[u] = 0u; qs[u] = 0;
                 if (k < S && rb + u < RPW && ray0 + rb + u < R) {
                     const float t = depth_at(nr[u], rg[u], k, S);
                     const float x = __fadd_rn(o[u][0], __fmul_rn(t, d[u][0])), y = __fadd_rn(o[u][1], __fmul_rn(t, d[u][1])),
@@ -480,30 +491,79 @@ __global__ void __launch_bounds__(256) cand_mark_kernel(const float* __restrict_
                     const int cx = g.sub == 2 ? sx >> 1 : sx, cy = g.sub == 2 ? sy >> 1 : sy, cz = g.sub == 2 ? sz >> 1 : sz;
                     if (sx >= 0 && cx < g.nx && sy >= 0 && cy < g.ny && sz >= 0 && cz < g.nz) {
                         const int q = (sz * (g.ny * g.sub) + sy) * (g.nx * g.sub) + sx;
-                        bit[u] = q & 31;
+                        bit[u] = q & 31; qs[u] = q;
                         word[u] = near_mask[q >> 5];
                     }
                 }
             }
+            bool cnd[kMarkRays];
+            int rank[kMarkRays];
+#pragma unroll
+            for (int u = 0; u < kMarkRays; ++u) {
+                cnd[u] = bit[u] >= 0 && (((dbg & 2) || ((word[u] >> bit[u]) & 1u)) && !(dbg & 1));
+                rank[u] = 0;
+            }
+            if constexpr (CELLS) {
+                int before[kMarkRays], same[kMarkRays];          // this lane's candidates of the same sub-cell: ahead of ray u, and in all
+#pragma unroll
+                for (int u = 0; u < kMarkRays; ++u) {
+                    before[u] = 0; same[u] = 0;
+#pragma unroll
+                    for (int v = 0; v < kMarkRays; ++v) {
+                        const bool eq = cnd[v] && qs[v] == qs[u];
+                        same[u] += eq ? 1 : 0;
+                        if (v < u) before[u] += eq ? 1 : 0;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kMarkRays; ++u)              // (every atomic is issued before the first rank is used)
+                    if (cnd[u] && before[u] == 0) rank[u] = atomicAdd(&sub_cnt[qs[u]], same[u]);
+#pragma unroll
+                for (int u = 1; u < kMarkRays; ++u)
+#pragma unroll
+                    for (int v = 0; v < u; ++v)
+                        if (cnd[u] && before[u] > 0 && cnd[v] && before[v] == 0 && qs[v] == qs[u]) rank[u] = rank[v] + before[u];
+            }
 #pragma unroll
             for (int u = 0; u < kMarkRays; ++u) {
                 const int ray = ray0 + rb + u;
-                const bool cand = bit[u] >= 0 && (((dbg & 2) || ((word[u] >> bit[u]) & 1u)) && !(dbg & 1));
+                const bool cand = cnd[u];
                 const unsigned long long cm = __ballot(cand);
                 if (rb + u < RPW && ray < R && lane == 0) ray_mask[(size_t)ray * NCH + ch] = 0ull;       // pass 2 ORs the valid bits in
                 if (cm) {
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&s_n, __popcll(cm));
                     base = __shfl(base, 0);
-                    if (cand) s_list[base + __popcll(cm & ((1ull << lane) - 1ull))] = ray * S + k;
+                    const int pos = base + __popcll(cm & ((1ull << lane) - 1ull));
+                    if constexpr (!CELLS) {
+                        if (cand) s_list[pos] = ray * S + k;
+                    } else {
+                        if (cand && pos < kCellStage) { s_list[pos] = ray * S + k; s_list[kCellStage + pos] = rank[u]; }
+                        // (more than kCellStage candidates in one workgroup -- half of its samples: this wave's share goes out at once, under its own reservation)
+                        const bool over = cand && pos >= kCellStage;
+                        const unsigned long long om = __ballot(over);
+                        if (om) {
+                            int gb = 0;
+                            if (lane == 0) gb = atomicAdd(cand_count, __popcll(om));
+                            gb = __shfl(gb, 0);
+                            const int64_t at = (int64_t)gb + __popcll(om & ((1ull << lane) - 1ull));
+                            if (over && at < list_cap) { arr_idx[at] = ray * S + k; arr_rank[at] = rank[u]; }
+                        }
+                    }
                 }
             }
         }
     }
     __syncthreads();
-    const int n = s_n;
+    const int n = CELLS ? min(s_n, kCellStage) : s_n;
     if (threadIdx.x == 0) s_base = n ? atomicAdd(cand_count, n) : 0;
     __syncthreads();
+    if constexpr (CELLS) {
+        const int64_t gb = s_base;
+        for (int i = threadIdx.x; i < n; i += 256)
+            if (gb + i < list_cap) { arr_idx[gb + i] = s_list[i]; arr_rank[gb + i] = s_list[kCellStage + i]; }
+        return;
+    }
     // a candidate's record = (x_s, its dense index): the position is evaluated HERE, one thread per candidate, with the same operations the
     // search used to repeat in all eight lanes of a group behind two more dependent loads (its list entry, then its ray) -- round 4
     const int64_t gb = s_base;
@@ -789,6 +849,140 @@ __global__ void __launch_bounds__(256, WAVES) cand_search_lists2_kernel(const fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The candidate search BY SUB-CELL.  cand_search_lists_kernel above re-reads a candidate's whole near list -- ~10 entry loads and ~40 dependent 16-byte
+// point gathers -- for every candidate, eight lanes each; on a body ~130 candidates share a sub-cell and so a list.  Here the candidates are grouped by
+// sub-cell first (counted in pass 1: cand_mark_kernel<.., true>), a wave takes up to 64 candidates of ONE sub-cell, reads the list and its points once
+// and tests them against one candidate per lane: ~2 lane-level loads per candidate instead of ~50, no shuffle reduction.  The same dist2_exact
+// comparisons on the same bits, the same lexicographic (d^2, vertex id) minimum: identical results.
+//   cell_ws (int32; SHERF_CELL_WS_INTS in include/sherf_hip.h): sub_cnt[NSUB] (zero on entry; cand_cells_alloc_kernel leaves it zero again: no fill launch per
+//   frame), sub_off[NSUB], cursors[4] (record cursor, item count; cleared by init_counters_kernel), items[item_cap] int2 = (first record, q | (n - 1) << 20).
+// Launches behind pass 1: allocate (thread per sub-cell: offsets + work items), place (thread per candidate: its record at sub_off[q] + rank), search.
+// ---------------------------------------------------------------------------------------------
+struct SherfCellWs { int32_t* sub_cnt; int32_t* sub_off; int32_t* cursors; int2* items; int64_t item_cap; };
+static inline int64_t sherf_cell_items(int R, int S) { return (int64_t)R * S / 64 + 1 + SHERF_NEAR_SUBCELLS; }   // sum of ceil(count / 64) <= candidates / 64 + occupied sub-cells
+static inline SherfCellWs sherf_cell_ws(int32_t* ws, int R, int S) {
+    return {ws, ws + SHERF_NEAR_SUBCELLS, ws + 2 * SHERF_NEAR_SUBCELLS, reinterpret_cast<int2*>(ws + 2 * SHERF_NEAR_SUBCELLS + 4), sherf_cell_items(R, S)};
+}
+
+// thread per sub-cell, as near_lists_alloc_kernel: the records' offset from ONE atomic per wave (the order among sub-cells is free), the count reset for the
+// next frame, and the sub-cell's work items -- chunks of up to 64 of its candidates -- from a second per-wave reservation
+__global__ void __launch_bounds__(256) cand_cells_alloc_kernel(const float* __restrict__ hdr, int32_t* __restrict__ sub_cnt, int32_t* __restrict__ sub_off,
+                                                               int32_t* __restrict__ cursors, int2* __restrict__ items, int64_t item_cap, int64_t list_cap) {
+    const CellGrid g = load_grid(hdr);
+    const int nsub = g.nx * g.ny * g.nz * g.sub * g.sub * g.sub;
+    if ((int)blockIdx.x * 256 >= ((nsub + 63) & ~63)) return;         // (whole workgroups beyond the grid; the launch covers SHERF_NEAR_SUBCELLS)
+    const int q = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int c = q < nsub ? sub_cnt[q] : 0;
+    if (c) sub_cnt[q] = 0;
+    const int nc = (c + 63) >> 6;
+    int incl = c, incl_i = nc;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off), vi = __shfl_up(incl_i, off);
+        if (lane >= off) { incl += v; incl_i += vi; }
+    }
+    const int total = __shfl(incl, 63), total_i = __shfl(incl_i, 63);
+    int base = 0, base_i = 0;
+    if (lane == 0 && total) {                                         // (both cursors in one 8-byte atomic: records in the low word, items in the high one, each < 2^31)
+        const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long*>(cursors), ((unsigned long long)total_i << 32) | (unsigned)total);
+        base = (int)(unsigned)old; base_i = (int)(old >> 32);
+    }
+    base = __shfl(base, 0); base_i = __shfl(base_i, 0);
+    if (c) {
+        const int64_t start = (int64_t)base + (incl - c), first = (int64_t)base_i + (incl_i - nc);
+        if (start + c <= list_cap && first + nc <= item_cap) {          // (cannot fail: the counts sum to the candidate count, which the list holds)
+            sub_off[q] = (int)start;
+            for (int j = 0; j < nc; ++j) items[first + j] = make_int2((int)start + 64 * j, q | ((min(64, c - 64 * j) - 1) << 20));
+        } else
+            sub_off[q] = -1;
+    }
+}
+
+// thread per candidate in arrival order: its record (x_s, dense index) -- evaluated with exactly the operations of cand_mark_kernel<.., false>'s tail -- lands
+// at sub_off[q] + rank of the candidate list, q from the same arithmetic on the same floats as pass 1
+__global__ void __launch_bounds__(256) cand_place_kernel(const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float* __restrict__ near,
+                                                         const float* __restrict__ far, int S, const float* __restrict__ Rg, const float* __restrict__ Th,
+                                                         const float* __restrict__ hdr, const int32_t* __restrict__ arr_idx, const int32_t* __restrict__ arr_rank,
+                                                         const int32_t* __restrict__ cand_count, const int32_t* __restrict__ sub_off,
+                                                         float4* __restrict__ cand_list, int64_t list_cap) {
+    const CellGrid g = load_grid(hdr);
+    const float fs = g.inv_cell * (float)g.sub;
+    const int snx = g.nx * g.sub, sny = g.ny * g.sub, snz = g.nz * g.sub;
+    const int64_t n = min((int64_t)*cand_count, list_cap);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int idx = arr_idx[i], rank = arr_rank[i];
+        const int ray = idx / S, k = idx - ray * S;
+        const float nr1 = near[ray], t = depth_at(nr1, __fsub_rn(far[ray], nr1), k, S);
+        const float x = __fadd_rn(ray_o[ray * 3], __fmul_rn(t, ray_d[ray * 3])), y = __fadd_rn(ray_o[ray * 3 + 1], __fmul_rn(t, ray_d[ray * 3 + 1])),
+                    z = __fadd_rn(ray_o[ray * 3 + 2], __fmul_rn(t, ray_d[ray * 3 + 2]));
+        float xs, ys, zs;
+        to_smpl_frame(x, y, z, Rg, Th, xs, ys, zs);
+        const int sx = (int)floorf((xs - g.ox) * fs), sy = (int)floorf((ys - g.oy) * fs), sz = (int)floorf((zs - g.oz) * fs);
+        if (sx < 0 || sx >= snx || sy < 0 || sy >= sny || sz < 0 || sz >= snz) continue;      // (pass 1 took it for a candidate inside the grid: not reached)
+        const int off = sub_off[(sz * sny + sy) * snx + sx];
+        const int64_t at = (int64_t)off + rank;
+        if (off >= 0 && at < list_cap) cand_list[at] = make_float4(xs, ys, zs, __int_as_float(idx));
+    }
+}
+
+// A persistent grid walks the item list with a static stride, one item per wave and step: the list's header once, the list's points staged in the wave's
+// own 1 KiB of LDS in blocks of 64 (lane e fetches entry e and its point), then every lane compares its own candidate with the staged points one after the
+// other -- LDS reads of one address broadcast, the trip count is the wave's.  The next item's descriptor, header and record are requested before this
+// item's points are compared.
+template <int NCH>
+__global__ void __launch_bounds__(256) cand_search_cells_kernel(const float4* __restrict__ cand_list, const int2* __restrict__ items,
+                                                                const int32_t* __restrict__ cursors, int64_t item_cap, int S,
+                                                                const int2* __restrict__ near_hdr, const uint16_t* __restrict__ near_list,
+                                                                const float4* __restrict__ cell_pts,
+                                                                unsigned long long* __restrict__ ray_mask, int32_t* __restrict__ dense_vid) {
+    __shared__ float4 s_pts[4][64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n_items = (int)min((int64_t)cursors[1], item_cap);
+    const unsigned long long kInit = ((unsigned long long)__float_as_uint(kThresh2) << 32) | 0x7FFFFFFFull;
+    const int stride = (int)gridDim.x * 4;
+    int it = (int)blockIdx.x * 4 + wave;
+    int2 item = items[it < n_items ? it : 0];
+    if (it >= n_items) return;
+    int2 h = near_hdr[item.y & 0xFFFFF];
+    float4 rec = cand_list[item.x + min(lane, item.y >> 20)];
+    for (; it < n_items; it += stride) {
+        const int n = (item.y >> 20) + 1, st = h.x, cn = h.y;
+        const bool live = lane < n;
+        const float xs = rec.x, ys = rec.y, zs = rec.z;
+        const int idx = __float_as_int(rec.w);
+        // the first block of this item's points, then the next item's chain
+        int e = lane;
+        float4 p = cell_pts[e < cn ? near_list[st + e] : 0];
+        const int itn = it + stride;
+        item = items[itn < n_items ? itn : 0];
+        h = near_hdr[item.y & 0xFFFFF];
+        rec = cand_list[item.x + min(lane, item.y >> 20)];
+        unsigned long long key = kInit;
+        for (int base = 0; base < cn; base += 64) {
+            __builtin_amdgcn_wave_barrier();         // (every lane has read the block before it is overwritten; LDS ordered by lgkmcnt)
+            s_pts[wave][lane] = p;
+            __builtin_amdgcn_wave_barrier();
+            e = base + 64 + lane;
+            if (base + 64 < cn) p = cell_pts[e < cn ? near_list[st + e] : 0];      // the next block's points, in flight over this block's comparisons
+            const int m = min(64, cn - base);
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+                const float4 v = s_pts[wave][j];
+                const float dd = dist2_exact(xs, ys, zs, v.x, v.y, v.z);
+                if (dd < kThresh2) {
+                    const unsigned long long cand = ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned)__float_as_int(v.w);
+                    key = cand < key ? cand : key;
+                }
+            }
+        }
+        if (live && (unsigned)(key >> 32) < __float_as_uint(kThresh2)) {
+            const int ray = idx / S, k = idx - ray * S;
+            dense_vid[idx] = (int)(key & 0x7FFFFFFFull);
+            atomicOr(&ray_mask[(size_t)ray * NCH + (k >> 6)], 1ull << (k & 63));
+        }
+    }
+}
+
 template <int NCH>
 __global__ void __launch_bounds__(1024) scan_chunk_mask_kernel(const uint64_t* __restrict__ ray_mask, int R, int32_t* __restrict__ cnt,
                                                                int32_t* __restrict__ base, int32_t* __restrict__ chunk_sum) {
@@ -877,10 +1071,12 @@ __global__ void __launch_bounds__(256) depth_minmax_kernel(const float* __restri
 
 // `sticky` (optional, the frame driver's): what the frame that used these counters before left in them is folded in before they are reset -- the largest valid-sample
 // count, the OR of the flag words, the number of frames folded -- so that a caller may look at its frames' flags every few frames instead of after every one.
-__global__ void init_counters_kernel(int32_t* counters, int32_t* cand_count, int32_t* sticky) {
+// `cell_cursors` (optional): the record cursor and the item count of the search by sub-cell (SherfCellWs).
+__global__ void init_counters_kernel(int32_t* counters, int32_t* cand_count, int32_t* sticky, int32_t* cell_cursors) {
     if (sticky) { sticky[0] = max(sticky[0], counters[0]); sticky[1] |= counters[3]; sticky[2] += 1; }
     counters[0] = 0; counters[1] = 0x7FFFFFFF; counters[2] = (int32_t)0x80000000; counters[3] = 0;
     *cand_count = 0;
+    if (cell_cursors) { cell_cursors[0] = 0; cell_cursors[1] = 0; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1094,7 +1290,8 @@ __global__ void __launch_bounds__(256) warp_geom_kernel(const int32_t* __restric
 int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const float* near, const float* far, int R, int S, const float* Rg, const float* Th,
                               const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
                               int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
-                              uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky);
+                              uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky,
+                              int32_t* cell_ws, int64_t cell_ws_len);
 int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
                          const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
                          int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);
@@ -1153,7 +1350,19 @@ extern "C" int sherf_sample_mask_nn(const float* ray_o, const float* ray_d, cons
                                        int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
                                        int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream) {
     return sherf_sample_mask_nn_impl(ray_o, ray_d, near, far, R, S, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt,
-                                     cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr);
+                                     cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr, nullptr, 0);
+}
+
+// sherf_sample_mask_nn with the workspace of the search by sub-cell (include/sherf_hip.h)
+extern "C" int sherf_sample_mask_nn_ws(const float* ray_o, const float* ray_d, const float* near, const float* far,
+                                       int R, int S, const float* Rg, const float* Th, const float* grid_hdr,
+                                       const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
+                                       int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
+                                       int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
+                                       int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, int32_t* cell_ws, int64_t cell_ws_len,
+                                       sherf_stream_t stream) {
+    return sherf_sample_mask_nn_impl(ray_o, ray_d, near, far, R, S, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt,
+                                     cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr, cell_ws, cell_ws_len);
 }
 
 // Pass 2 of the two-pass sampler and the first scan kernel, on the candidate list some pass 1 left in `cand_list` (records (x_s, dense index), index = row * S + k):
@@ -1192,7 +1401,7 @@ static void search_and_scan(hipStream_t st, int R, int S, const float* grid_hdr,
 // The point sampler's use of this file's machinery (csrc/field.hip: sherf_points_mask_nn_impl; `rows` rows of 64 points).  _begin resets the counters and the
 // candidate count ahead of point_mark_kernel; _search runs the candidate search and both scan kernels behind it: counters[0] = the valid points.
 int sherf_points_begin_impl(int32_t* counters, int32_t* scan_ws, int rows, int32_t* sticky, sherf_stream_t stream) {
-    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream), counters, sherf_scan_ws(scan_ws, rows).cand_count, sticky);
+    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream), counters, sherf_scan_ws(scan_ws, rows).cand_count, sticky, static_cast<int32_t*>(nullptr));
     SHERF_LAUNCH_CHECK();
 }
 int sherf_points_search_impl(int rows, const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const float* cand_list, int64_t list_cap,
@@ -1211,8 +1420,10 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
                               const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
                               int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
                               int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
-                              int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky) {
+                              int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky,
+                              int32_t* cell_ws, int64_t cell_ws_len) {
     SHERF_CHECK_ARG(ray_o && ray_d && near && far && Rg && Th && grid_hdr && cell_start && cell_pts && near_mask);
+    SHERF_CHECK_ARG(cell_ws == nullptr || (cell_ws_len >= SHERF_CELL_WS_INTS(R, S) && (reinterpret_cast<uintptr_t>(cell_ws) & 7) == 0));
     SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && cs_vid && cs_xs && dense_vid && ray_mask && scan_ws);
     SHERF_CHECK_ARG(R > 0 && S >= 2 && S <= 256 && (int64_t)R * S < 2147483647LL && capacity > 0 && (near_hdr == nullptr) == (near_list == nullptr));
     hipStream_t st = as_stream(stream);
@@ -1223,20 +1434,39 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
     int32_t* chunk_sum = sw.chunk_sum;          // [n_chunks]
     const float4* cp = reinterpret_cast<const float4*>(cell_pts);
     int32_t* cand_count = sw.cand_count;
-    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, st, counters, cand_count, sticky);
-    hipLaunchKernelGGL(depth_minmax_kernel, dim3(min(256, cdiv(R, 256))), dim3(256), 0, st, near, far, R, S, counters);
     // two passes over a dense candidate list (see cand_mark_kernel) whenever the list -- `capacity` records in cs_xs, which the
     // compaction below only writes afterwards -- provably holds every sample; sherf_set_debug bit 9 forces the one-wave-per-ray kernel
     const bool two_pass = !(g_sherf_debug & 512) && capacity >= (int64_t)R * S;
+    // the search by sub-cell (cand_search_cells_kernel) wherever its workspace and the near lists are there; sherf_set_debug bit 28 keeps the search
+    // by candidate (cand_search_lists_kernel) for A/B runs, as do the bits that select one of its variants
+    const bool cells = two_pass && cell_ws && near_hdr && near_list && !(g_sherf_debug & (16384 | kDebugSearchByCandidate)) && !(sherf_experiment() & 16384);
+    const SherfCellWs cw = sherf_cell_ws(cell_ws, R, S);
+    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, st, counters, cand_count, sticky, cells ? cw.cursors : static_cast<int32_t*>(nullptr));
+    hipLaunchKernelGGL(depth_minmax_kernel, dim3(min(256, cdiv(R, 256))), dim3(256), 0, st, near, far, R, S, counters);
     if (two_pass) {
         float4* cand_list = reinterpret_cast<float4*>(cs_xs);            // one 16-byte record per candidate: the list holds `capacity` of them
         const int64_t list_cap = capacity;
+        int32_t* const no_i32 = nullptr;
+        // workgroups per CU of the persistent search by sub-cell (debug bits 20-23 override, as for the search by candidate)
+        const int cells_wgs = ((g_sherf_debug >> 20) & 15) ? ((g_sherf_debug >> 20) & 15) : kCellSearchWgs;
 #define SHERF_TWO_PASS(N)                                                                                                          \
-        hipLaunchKernelGGL(cand_mark_kernel<N>, dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th,    \
-                           grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug);                         \
-        search_and_scan<N>(st, R, S, grid_hdr, cell_start, cp, cand_list, list_cap, cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, base_local, \
-                           chunk_sum)
-        if (nch == 1) { SHERF_TWO_PASS(1); } else if (nch == 2) { SHERF_TWO_PASS(2); } else if (nch == 3) { SHERF_TWO_PASS(3); } else { SHERF_TWO_PASS(4); }
+        if (cells) {                                                                                                               \
+            hipLaunchKernelGGL((cand_mark_kernel<N, true>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
+                               grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug, cw.sub_cnt, cs_idx, cs_vid); \
+            hipLaunchKernelGGL(cand_cells_alloc_kernel, dim3(SHERF_NEAR_SUBCELLS / 256), dim3(256), 0, st, grid_hdr, cw.sub_cnt, cw.sub_off, cw.cursors, \
+                               cw.items, cw.item_cap, list_cap);                                                                   \
+            hipLaunchKernelGGL(cand_place_kernel, dim3(min(8 * n_cus(), cdiv((int64_t)R * S, 256))), dim3(256), 0, st, ray_o, ray_d, near, far, S, Rg, Th, \
+                               grid_hdr, cs_idx, cs_vid, cand_count, cw.sub_off, cand_list, list_cap);                             \
+            hipLaunchKernelGGL(cand_search_cells_kernel<N>, dim3(cells_wgs * n_cus()), dim3(256), 0, st, cand_list, cw.items, cw.cursors, cw.item_cap, S, \
+                               reinterpret_cast<const int2*>(near_hdr), near_list, cp, reinterpret_cast<unsigned long long*>(ray_mask), dense_vid); \
+            hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(cdiv(R, 1024)), dim3(1024), 0, st, ray_mask, R, ray_cnt, base_local, chunk_sum); \
+        } else {                                                                                                                   \
+            hipLaunchKernelGGL((cand_mark_kernel<N, false>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
+                               grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug, no_i32, no_i32, no_i32); \
+            search_and_scan<N>(st, R, S, grid_hdr, cell_start, cp, cand_list, list_cap, cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, base_local, \
+                               chunk_sum);                                                                                         \
+        }
+        if (nch == 1) { SHERF_TWO_PASS(1) } else if (nch == 2) { SHERF_TWO_PASS(2) } else if (nch == 3) { SHERF_TWO_PASS(3) } else { SHERF_TWO_PASS(4) }
 #undef SHERF_TWO_PASS
     } else {
     // 10 KiB of unused dynamic LDS per workgroup: caps the sampler at 6 workgroups per CU (6 of the 8 wave slots per SIMD).  The

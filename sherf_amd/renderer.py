@@ -206,6 +206,8 @@ class _Workspace:
             # sherf_build_near_lists: (start, count) per sub-cell of the near mask + the cursor; u16 vertex lists (worst case, never grown)
             near_hdr=torch.zeros(2 * NEAR_SUBCELLS + 2, **i32),
             near_list=torch.zeros(125 * V + 3 * NEAR_SUBCELLS, dtype=torch.int16, device=dev),
+            # the candidate search by sub-cell (SHERF_CELL_WS_INTS): per-sub-cell counts (zero here, left zero by every frame) and offsets, the work items
+            cell_ws=torch.zeros(4 * NEAR_SUBCELLS + 6 + 2 * (R * S // 64), **i32),
         )
         self.key, self.t = key, t
         self.desc = None
@@ -252,7 +254,7 @@ class _Workspace:
 
     STATIC_FIELDS = ('A', 'posefeat', 'PO', 'SO', 'T2C', 'C2S', 'grid_hdr', 'cell_start', 'cell_pts', 'cell_scratch', 'near_mask',
                      'counters', 'ray_base', 'ray_cnt', 'cs_idx', 'cs_vid', 'cs_xs', 'dense_vid', 'ray_mask', 'scan_ws', 'geom',
-                     'cs_tvid', 'tokens', 'extras', 'sample_out')
+                     'cs_tvid', 'tokens', 'extras', 'sample_out', 'cell_ws')
 
     def descriptor(self, smpl):
         """The `sherf_frame` of this workspace with every field that does not change from frame to frame filled in ONCE (workspace and
@@ -265,6 +267,7 @@ class _Workspace:
         for k in self.STATIC_FIELDS:
             setattr(fr, k, A(self.t[k]))
         fr.sticky = A(self.t['counters']) + 16
+        fr.cell_ws_len = self.t['cell_ws'].numel()
         fr.J_template, fr.J_shapedirs, fr.parents = A(smpl['J_template']), A(smpl['J_shapedirs']), A(smpl['parents_i32'])
         fr.posedirs, fr.shapedirs, fr.weights = A(smpl['posedirs_flat']), A(smpl['shapedirs']), A(smpl['weights'])
         self.desc = (self.t, smpl, fr, dict(near_hdr=A(self.t['near_hdr']), near_list=A(self.t['near_list']), near_cap=self.t['near_list'].numel()))
