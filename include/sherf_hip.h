@@ -575,6 +575,71 @@ typedef struct {
 int sherf_query_field(const sherf_frame* frame, const sherf_field_query* query, sherf_vox_level* levels_out_host,
                       sherf_stream_t stream_main, sherf_stream_t stream_side, sherf_stream_t stream_aux);
 
+/* ---------------------------------------------------------------------------------------------
+ * Importance sampling: the fine pass of ImportanceRenderer.forward (renderer.py:373-393 with its two broken calls repaired: the coarse marcher call gets the
+ * ray directions as :395 passes them, and the fine samples o + depths_fine d go through what the coarse ones went through in :304-371 -- what the field query
+ * computes).  csrc/importance.hip, csrc/composite.hip, csrc/frame.hip.  Inference only.
+ *
+ * sherf_importance_depths: sample_importance / sample_pdf (renderer.py:483-542) on a frame's compact coarse samples (ray_base / ray_cnt / cs_idx / sample_out
+ *   as sherf_sample_mask_nn and the network left them; near / far / S give the analytic coarse depths).  Per ray: the coarse compositing weights by
+ *   sherf_composite_compact's operations in its order (a rejected sample's weight is exactly 0; `white_back` carries the clamp mode, bit 0 is ignored),
+ *   max_pool1d(2, 1, padding 1), avg_pool1d(2, 1), + 0.01, the S - 2 inner weights over the S - 1 mid-point bins, + 1e-5, pdf, cdf, and for every u[r][j] the
+ *   right-sided search, the two clamps, denom < 1e-5 -> 1 and the linear interpolation -- these steps in fp64 -- then the N results sorted:
+ *   depths_fine[r][0..N) ascending, every value within [(z_0 + z_1) / 2, (z_{S-2} + z_{S-1}) / 2] of its own ray, never NaN.  u[R][N] in [0, 1] (the caller's
+ *   to check).  A ray whose coarse samples lie beyond tok_cap (not evaluated) is treated as empty: the uniform pdf.  points (may be NULL, then ray_o is NULL
+ *   too): [R * N][3] = ray_o + depths_fine * ray_d formed as a frame forms its samples (one product, one sum, fp32), the input of sherf_points_mask_nn.
+ *   3 <= S <= 256, 1 <= N <= 256, R * S and R * N < 2^31, non-null pointers, else SHERF_EINVAL before anything is launched (S = 2 leaves no inner weight). */
+int sherf_importance_depths(const int32_t* ray_base, const int32_t* ray_cnt, const int32_t* cs_idx, const float* sample_out,
+                            const float* ray_o, const float* ray_d, const float* near, const float* far, int R, int S,
+                            int white_back, int64_t tok_cap, const float* u, int N, float* depths_fine, float* points,
+                            sherf_stream_t stream);
+/* points[R * N][3] = ray_o + depths_fine * ray_d for depths handed in: the second half of sherf_importance_depths alone (same operations, same bits).  What
+ * sherf_render_frame_importance runs in its place when importance->u is NULL.  R > 0, 1 <= N <= 256, R * N < 2^31, non-null pointers, else SHERF_EINVAL. */
+int sherf_importance_points(const float* ray_o, const float* ray_d, const float* depths_fine, int R, int N, float* points,
+                            sherf_stream_t stream);
+/* sherf_composite_merged: unify_samples + MipRayMarcher2 (renderer.py:389-393) without materialising the merged lists.  Per ray the S analytic coarse depths
+ *   and depths_fine[r][0..N) (ASCENDING; the caller's to guarantee) are walked in merged order -- on equal depths a coarse sample goes before a fine one and
+ *   fine samples keep their order: the stable order of the concatenation.  Every depth takes part in the deltas whatever its mask; the last of the S + N takes
+ *   1e10.  Only valid samples are read: coarse ones from (ray_base, ray_cnt, cs_idx, sample_out) as sherf_composite_compact_cap reads them, fine sample (r, j)
+ *   = point r N + j of a sherf_points_mask_nn run over R * N points: valid if bit (r N + j) & 63 of fine_mask[(r N + j) >> 6] is set, its row of fine_out found
+ *   from fine_base as sherf_field_scatter finds it.  Outputs as sherf_composite_compact_cap (rgb * 2 - 1, depth after nan_to_num and the global clamp, acc);
+ *   bit-identical to sherf_composite_dense on the same samples merged and scattered densely.  counters[1..2] (the frame's depth range, ordered ints) are
+ *   first widened by the fine depths, so the clamp runs over all S + N depths of the frame.  A ray with a valid sample beyond tok_cap (coarse) or
+ *   fine_tok_cap (fine) is written as NaN and counters[3] |= 2; neither sample_out nor fine_out is read beyond its capacity. */
+int sherf_composite_merged(int32_t* counters, const int32_t* ray_base, const int32_t* ray_cnt, const int32_t* cs_idx,
+                           const float* sample_out, int64_t tok_cap, const float* depths_fine, const uint64_t* fine_mask,
+                           const int32_t* fine_base, const float* fine_out, int64_t fine_tok_cap, const float* ray_d,
+                           const float* near, const float* far, int R, int S, int N, int white_back, float* rgb, float* depth,
+                           float* acc, sherf_stream_t stream);
+/* The two-pass frame as ONE native call.  sherf_importance names the draws, the fine depths and the fine pass's OWN buffers: the point sampler's (as
+ * sherf_points_mask_nn documents them for R * n points: capacity >= R * n rounded up to whole rows of 64) and the token side's (as sherf_frame's, for
+ * tok_capacity samples; 0: capacity), with their own counters [4] (counters[0] = the fine pass's valid samples).  sherf_render_frame_importance enqueues, in
+ * this order: phase 1 of `frame` (everything up to the coarse network; SHERF_FRAME_REUSE_OBSERVATION applies to it as to any frame),
+ * sherf_importance_depths (writing `points`), the fine pass -- sherf_points_mask_nn on `points`, the warp with one direction per ray, the gather and the
+ * network in the plain whole-launch form of frame->mlp_prec (SHERF_FRAME_MLP_PIPELINED / _TWO_TILES / the OSG decoder honoured; the split, parts,
+ * PE-fragment and exact-grid forms are coarse-only), reading the cell lists, near lists, SMPL tables, folded tables and voxel levels phase 1 has just built:
+ * the encoder and the folds run once per frame -- and sherf_composite_merged into frame->rgb / depth / acc.  All of the fine pass runs on stream_main.
+ * SHERF_FRAME_REPORT_COUNT reports both counts: sherf_frame_count the coarse one as for any frame, sherf_importance_count {coarse, fine} after waiting for
+ * the fine pass's sampler.  Never captured as a graph; while sherf_profile_frames is on the call is refused (SHERF_EINVAL: the ring's fields describe a one-pass
+ * frame).  The fine pass's network raises its flags in importance->counters[3], not in frame->counters[3].  importance->n in 1..256, frame->S in 3..256, non-null pointers, capacity >= R * n, else SHERF_EINVAL
+ * before anything is enqueued. */
+typedef struct {
+    int32_t n, pad_;            /* fine samples per ray */
+    const float* u;             /* [R][n] draws in [0, 1]; NULL: depths_fine is an INPUT (ascending per ray, the caller's to guarantee) and only `points` is formed */
+    float* depths_fine;         /* [R][n] out, ascending per ray */
+    float* points;              /* [R * n][3] out: the fine samples' positions */
+    int64_t capacity;           /* rows of cs_idx / cs_vid / cs_xs (>= R * n) */
+    int64_t tok_capacity;       /* rows of geom / tokens / extras / sample_out (0: capacity) */
+    int32_t* counters; int32_t* ray_base; int32_t* ray_cnt; int32_t* cs_idx; int32_t* cs_vid; float* cs_xs;
+    int32_t* dense_vid; uint64_t* ray_mask; int32_t* scan_ws;
+    float* geom; int32_t* cs_tvid; float* tokens; float* extras; float* sample_out;
+} sherf_importance;
+int sherf_render_frame_importance(const sherf_frame* frame, const sherf_importance* importance, sherf_vox_level* levels_out_host,
+                                  sherf_stream_t stream_main, sherf_stream_t stream_side, sherf_stream_t stream_aux);
+/* {coarse, fine} valid-sample counts of the last sherf_render_frame_importance call THE CALLING THREAD enqueued on the current device with
+ * SHERF_FRAME_REPORT_COUNT: waits for the fine pass's sampler of that frame only; slots and the overtaken rule as sherf_frame_count. */
+int sherf_importance_count(int32_t* nv2_host);
+
 /* The valid-sample count of the last frame THE CALLING THREAD enqueued on the current device with SHERF_FRAME_REPORT_COUNT (waits for the
  * sampler of that frame, not for the frame; other threads' frames on the device have their own slots -- a ring of eight per device -- and the
  * wait holds no lock; a thread whose frame has been overtaken by eight later REPORT_COUNT frames on the device gets SHERF_EINVAL instead of
@@ -599,7 +664,8 @@ int sherf_frame_observation_stats(int64_t* stats_host, int32_t n);
  * nearest vertex, compaction: counters[0] = the frame's number of valid samples) -- what a caller runs once to size tok_capacity. */
 /* stream_aux (may be NULL): a third stream on which the occupancy structure of voxel levels 1-3 is built while the
  * level-0 convolutions run on stream_side. */
-/* sizeof of {sherf_vox_level, sherf_svox_level_ws, sherf_svox_layer, sherf_svox_plan, sherf_frame} for binding checks */
+/* sizeof of {sherf_vox_level, sherf_svox_level_ws, sherf_svox_layer, sherf_svox_plan, sherf_frame} for binding checks (n >= 5); n >= 6: sherf_importance
+ * as well -- later structs are appended, an entry never moves */
 int sherf_struct_sizes(int32_t* sizes_host, int32_t n);
 /* HIP-event timeline of the frames issued by sherf_render_frame (roofline measurement on the launch streams, without a
  * profiler's launch overhead): enable != 0 starts recording into a ring of 64 frames; read synchronises and returns, per

@@ -83,7 +83,14 @@ class FieldQuery(ctypes.Structure):                   # sherf_field_query (sherf
     _fields_ = [('points', _vp), ('dirs', _vp), ('n', _i64), ('rgb', _vp), ('sigma', _vp), ('mask', _vp)]
 
 
+class Importance(ctypes.Structure):                   # sherf_importance (sherf_render_frame_importance)
+    _fields_ = [('n', _i32), ('pad_', _i32), ('u', _vp), ('depths_fine', _vp), ('points', _vp), ('capacity', _i64), ('tok_capacity', _i64)] + \
+               [(n, _vp) for n in ('counters', 'ray_base', 'ray_cnt', 'cs_idx', 'cs_vid', 'cs_xs', 'dense_vid', 'ray_mask', 'scan_ws',
+                                   'geom', 'cs_tvid', 'tokens', 'extras', 'sample_out')]
+
+
 _STRUCTS = (VoxLevel, SvoxLevelWs, SvoxLayer, SvoxPlan, Frame)
+_STRUCTS_MORE = (Importance,)                         # sherf_struct_sizes' entries behind the first five (appended, never moved)
 
 
 # the `white_back` bit field of the compositing entry points and of sherf_frame (include/sherf_hip.h: SHERF_COMPOSITE_*)
@@ -158,10 +165,11 @@ def _init():
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.restype = ret
         fn.argtypes = [a[0] for a in args]
-    sizes = (ctypes.c_int32 * len(_STRUCTS))()
-    if lib.sherf_struct_sizes(sizes, len(_STRUCTS)) != 0 or [int(v) for v in sizes] != [ctypes.sizeof(c) for c in _STRUCTS]:
+    structs = _STRUCTS + _STRUCTS_MORE
+    sizes = (ctypes.c_int32 * len(structs))()
+    if lib.sherf_struct_sizes(sizes, len(structs)) != 0 or [int(v) for v in sizes] != [ctypes.sizeof(c) for c in structs]:
         raise RuntimeError(f'struct layout mismatch between include/sherf_hip.h and sherf_amd/_lib.py: '
-                           f'{[int(v) for v in sizes]} vs {[ctypes.sizeof(c) for c in _STRUCTS]}')
+                           f'{[int(v) for v in sizes]} vs {[ctypes.sizeof(c) for c in structs]}')
     _lib = lib
     return lib
 

@@ -258,6 +258,118 @@ __global__ void __launch_bounds__(256) composite_dense_bwd_kernel(const float* _
     }
 }
 
+// Compositing over TWO sample lists merged by depth (importance sampling: unify_samples + MipRayMarcher2, renderer.py:389-393, 446-456): a ray's S analytic
+// coarse depths and the N ascending depths of depths_fine[r], walked in merged order -- a coarse sample before a fine one of the same depth, fine samples in
+// their stored order (the stable order of the concatenation [coarse, fine]; torch.sort promises none, so the goldens hold no tie).  EVERY depth takes part in
+// the deltas, whatever its mask: a valid sample's delta is the distance to the next depth of the merged list, the last of the S + N takes 1e10.  Only valid
+// samples are read and enter the products -- coarse ones from the frame's compact list as in composite_compact_kernel, fine ones from the point sampler's
+// rows of 64 (point r N + j; csrc/field.hip: field_scatter_kernel finds a point's compact row the same way); a rejected sample's weight is exactly 0 and its
+// transmittance factor exactly 1 (file header).  Same arithmetic in the same order as composite_dense_kernel on the merged, densely scattered samples.
+// A ray with no valid sample in either list skips the walk: the loop would leave every accumulator at its initial value.
+// Token overflow in either list: NaN pixels + flag bit 1, as composite_compact_kernel.
+template <int MODE>
+__global__ void __launch_bounds__(256) composite_merged_kernel(const int32_t* __restrict__ counters, const int32_t* __restrict__ ray_base,
+                                                               const int32_t* __restrict__ ray_cnt, const int32_t* __restrict__ cs_idx,
+                                                               const float4* __restrict__ sample_out, int64_t tok_cap,
+                                                               const float* __restrict__ depths_fine, const uint64_t* __restrict__ fine_mask,
+                                                               const int32_t* __restrict__ fine_base, const float4* __restrict__ fine_out,
+                                                               int64_t fine_tok_cap, const float* __restrict__ ray_d, const float* __restrict__ near,
+                                                               const float* __restrict__ far, int R, int S, int N, int white_back,
+                                                               int32_t* __restrict__ flags, float* __restrict__ rgb, float* __restrict__ depth,
+                                                               float* __restrict__ acc) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const float qnan = __int_as_float(0x7fc00000);
+    const int base = ray_base[r], cnt = ray_cnt[r];
+    bool bad = (int64_t)base + cnt > tok_cap;
+    // the ray's fine points: bits r N .. r N + N - 1 of the rows' mask words
+    const int64_t p0 = (int64_t)r * N, p1 = p0 + N;
+    bool any_fine = false;
+    for (int64_t row = p0 >> 6; row <= (p1 - 1) >> 6; ++row) {
+        uint64_t m = fine_mask[row];
+        const int64_t lo = row << 6;
+        if (p0 > lo) m &= ~0ull << (p0 - lo);
+        if (p1 < lo + 64) m &= (1ull << (p1 - lo)) - 1ull;
+        if (m) {
+            any_fine = true;
+            const int top = 63 - __builtin_clzll(m);                                      // the ray's last valid point of this row
+            if ((int64_t)fine_base[row] + __popcll(fine_mask[row] & ((1ull << top) - 1ull)) >= fine_tok_cap) bad = true;
+        }
+    }
+    if (bad) {
+        rgb[r * 3] = rgb[r * 3 + 1] = rgb[r * 3 + 2] = qnan; depth[r] = qnan; acc[r] = qnan;
+        if (flags) atomicOr(flags, 2);
+        return;
+    }
+    const float dmin = ord2f(counters[1]), dmax = ord2f(counters[2]);
+    float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, wsum = 0.f, dsum = 0.f;
+    if (cnt > 0 || any_fine) {
+        const float d0 = ray_d[r * 3], d1 = ray_d[r * 3 + 1], d2 = ray_d[r * 3 + 2];
+        const float dn = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+        const float nr = near[r], range = __fsub_rn(far[r], nr);
+        const float* tf = depths_fine + (size_t)r * N;
+        const float inf = __int_as_float(0x7f800000);
+        int k = 0, j = 0, ci = 0;                                     // heads: coarse depth, fine depth, coarse compact sample
+        int knext = cnt > 0 ? cs_idx[base] - r * S : -1;              // dense index of the next valid coarse sample
+        int64_t row = -1;
+        uint64_t word = 0;
+        int rbase = 0;
+        float tc = depth_at(nr, range, 0, S), tn = tf[0];
+        for (int step = 0; step < S + N; ++step) {
+            const bool coarse = k < S && (j >= N || tc <= tn);        // (a tie: the coarse sample first)
+            const float t = coarse ? tc : tn;
+            bool valid = false;
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (coarse) {
+                if (k == knext) {
+                    valid = true;
+                    o = sample_out[base + ci];
+                    ++ci;
+                    knext = ci < cnt ? cs_idx[base + ci] - r * S : -1;
+                }
+                ++k;
+                tc = k < S ? depth_at(nr, range, k, S) : inf;
+            } else {
+                const int64_t p = p0 + j;
+                if ((p >> 6) != row) { row = p >> 6; word = fine_mask[row]; rbase = fine_base[row]; }
+                const int b = (int)(p & 63);
+                if ((word >> b) & 1ull) {
+                    valid = true;
+                    o = fine_out[(int64_t)rbase + __popcll(word & ((1ull << b) - 1ull))];
+                }
+                ++j;
+                tn = j < N ? tf[j] : inf;
+            }
+            if (!valid) continue;
+            const bool last = k >= S && j >= N;
+            const float tnext = (k < S && (j >= N || tc <= tn)) ? tc : tn;
+            const float delta = (last ? 1e10f : tnext - t) * dn;
+            const float alpha = 1.f - expf(-(density<MODE>(o.w) * delta));
+            const float w = alpha * T;
+            T = T * (1.f - alpha + 1e-10f);
+            cr += w * o.x; cg += w * o.y; cb += w * o.z; wsum += w; dsum += w * t;
+        }
+    }
+    float dep = dsum / wsum;                                   // 0/0 -> NaN for empty rays
+    if (dep != dep) dep = __int_as_float(0x7f800000);          // nan_to_num(.., inf)
+    dep = fminf(fmaxf(dep, dmin), dmax);
+    if (white_back) { cr += 1.f - wsum; cg += 1.f - wsum; cb += 1.f - wsum; }
+    rgb[r * 3] = cr * 2.f - 1.f; rgb[r * 3 + 1] = cg * 2.f - 1.f; rgb[r * 3 + 2] = cb * 2.f - 1.f;
+    depth[r] = dep;
+    acc[r] = wsum;
+}
+
+// The frame's depth range (counters[1..2], ordered ints: ray_marcher.py:57 clamps with the min / max over ALL S + N depths) widened by the fine depths: a
+// ray's are ascending, so its first and last.  sherf_importance_depths keeps every fine depth inside its own ray's coarse span and this changes nothing
+// then; depths from elsewhere (the unit tests put a fine sample behind the last coarse one) are folded in.  A wave reduces, lane 0 issues the two atomics.
+__global__ void __launch_bounds__(256) fine_range_kernel(const float* __restrict__ depths_fine, int R, int N, int32_t* __restrict__ counters) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    int lo = 0x7fffffff, hi = (int)0x80000000;
+    if (r < R) { lo = f2ord(depths_fine[(size_t)r * N]); hi = f2ord(depths_fine[(size_t)r * N + N - 1]); }
+    for (int m = 32; m > 0; m >>= 1) { lo = min(lo, __shfl_xor(lo, m)); hi = max(hi, __shfl_xor(hi, m)); }
+    if ((threadIdx.x & 63) == 0) { atomicMin(counters + 1, lo); atomicMax(counters + 2, hi); }
+}
+
 // bit 0 of the entry points' `white_back`: white background; bit 1: clamp_mode 'softplus' (include/sherf_hip.h); anything else is refused
 constexpr int kCompositeBits = SHERF_COMPOSITE_WHITE_BACK | SHERF_COMPOSITE_SOFTPLUS;
 
@@ -354,5 +466,27 @@ extern "C" int sherf_composite_compact_bwd(const int32_t* ray_base, const int32_
     hipLaunchKernelGGL(composite_compact_bwd_kernel<CLAMP_RELU>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), ray_base, ray_cnt, cs_idx,
                        reinterpret_cast<const float4*>(sample_out), ray_d, near, far, R, S, wb, d_rgb, d_acc,
                        reinterpret_cast<float4*>(d_sample_out));
+    SHERF_LAUNCH_CHECK();
+}
+
+extern "C" int sherf_composite_merged(int32_t* counters, const int32_t* ray_base, const int32_t* ray_cnt, const int32_t* cs_idx,
+                                      const float* sample_out, int64_t tok_cap, const float* depths_fine, const uint64_t* fine_mask,
+                                      const int32_t* fine_base, const float* fine_out, int64_t fine_tok_cap, const float* ray_d,
+                                      const float* near, const float* far, int R, int S, int N, int white_back, float* rgb, float* depth,
+                                      float* acc, sherf_stream_t stream) {
+    SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && sample_out && depths_fine && fine_mask && fine_base && fine_out);
+    SHERF_CHECK_ARG(ray_d && near && far && rgb && depth && acc);
+    SHERF_CHECK_ARG(R > 0 && S >= 2 && N >= 1 && tok_cap > 0 && fine_tok_cap > 0 && (int64_t)R * N < 2147483648LL && (int64_t)R * S < 2147483648LL);
+    SHERF_CHECK_ARG((white_back & ~kCompositeBits) == 0);
+    const int wb = white_back & SHERF_COMPOSITE_WHITE_BACK;
+    hipLaunchKernelGGL(fine_range_kernel, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), depths_fine, R, N, counters);
+    if (white_back & SHERF_COMPOSITE_SOFTPLUS)
+        hipLaunchKernelGGL(composite_merged_kernel<CLAMP_SOFTPLUS>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base, ray_cnt,
+                           cs_idx, reinterpret_cast<const float4*>(sample_out), tok_cap, depths_fine, fine_mask, fine_base,
+                           reinterpret_cast<const float4*>(fine_out), fine_tok_cap, ray_d, near, far, R, S, N, wb, counters + 3, rgb, depth, acc);
+    else
+        hipLaunchKernelGGL(composite_merged_kernel<CLAMP_RELU>, dim3(cdiv(R, 256)), dim3(256), 0, as_stream(stream), counters, ray_base, ray_cnt,
+                           cs_idx, reinterpret_cast<const float4*>(sample_out), tok_cap, depths_fine, fine_mask, fine_base,
+                           reinterpret_cast<const float4*>(fine_out), fine_tok_cap, ray_d, near, far, R, S, N, wb, counters + 3, rgb, depth, acc);
     SHERF_LAUNCH_CHECK();
 }

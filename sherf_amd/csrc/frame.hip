@@ -40,6 +40,8 @@ struct DevState {
     hipEvent_t ev_start, ev_smpl, ev_enc, ev_mid, ev_fold, ev_lev[8], ev_cnt, ev_part[kMaxParts], ev_mlp;
     int32_t* host_nv = nullptr;      // pinned: the frame's valid-sample count for SHERF_FRAME_EXACT_GRIDS
     hipEvent_t ev_rep[8];            // SHERF_FRAME_REPORT_COUNT: a ring of (pinned word, event) pairs; host_nv[8 + slot]
+    bool rep_fine[8] = {false, false, false, false, false, false, false, false};   // the slot's frame is an importance frame (ev_rep2 recorded)
+    hipEvent_t ev_rep2[8];           // the same slot's second pair for an importance frame: the fine pass's count, host_nv[16 + slot]
     int rep_next = 0;
     unsigned long long rep_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rep_counter = 0;   // which frame holds a slot: a reader whose frame has been overtaken by eight others is told so
     hipStream_t cap_stream = nullptr;   // frame graphs are CAPTURED on this library-owned non-blocking stream (the caller's may be the legacy default
@@ -71,6 +73,7 @@ extern "C" int sherf_struct_sizes(int32_t* sizes_host, int32_t n) {
     sizes_host[2] = (int32_t)sizeof(sherf_svox_layer);
     sizes_host[3] = (int32_t)sizeof(sherf_svox_plan);
     sizes_host[4] = (int32_t)sizeof(sherf_frame);
+    if (n >= 6) sizes_host[5] = (int32_t)sizeof(sherf_importance);
     return SHERF_OK;
 }
 
@@ -104,7 +107,8 @@ extern "C" int sherf_profile_frames_read(float* ms_host, int32_t max_n, int32_t*
     return SHERF_OK;
 }
 
-extern "C" int sherf_frame_count(int32_t* nv_host) {
+// `fine`: the importance frame's second pair of the slot -> nv_host[0..1] = {coarse, fine}
+static int frame_count_impl(int32_t* nv_host, bool fine) {
     SHERF_CHECK_ARG(nv_host);
     int dev = 0;
     SHERF_HIP_CHECK(hipGetDevice(&dev));
@@ -119,18 +123,23 @@ extern "C" int sherf_frame_count(int32_t* nv_host) {
     {
         std::lock_guard<std::mutex> frame_lock(g_frame_mu);
         SHERF_CHECK_ARG(d.init && slot >= 0);
+        SHERF_CHECK_ARG(!fine || d.rep_fine[slot]);          // (the thread's last frame was not an importance frame)
         if (d.rep_seq[slot] != t_rep_seq[dev]) return overtaken();
-        ev = d.ev_rep[slot];
+        ev = fine ? d.ev_rep2[slot] : d.ev_rep[slot];
     }
     SHERF_HIP_CHECK(hipEventSynchronize(ev));          // (no lock held: other threads keep enqueueing; the ring has 8 slots per device)
-    const int32_t nv = d.host_nv[8 + slot];
+    const int32_t nv = d.host_nv[8 + slot], nvf = d.host_nv[16 + slot];
     {
         std::lock_guard<std::mutex> frame_lock(g_frame_mu);     // the word is this frame's only if nobody took the slot while we waited
         if (d.rep_seq[slot] != t_rep_seq[dev]) return overtaken();
     }
-    *nv_host = nv;
+    nv_host[0] = nv;
+    if (fine) nv_host[1] = nvf;
     return SHERF_OK;
 }
+
+extern "C" int sherf_frame_count(int32_t* nv_host) { return frame_count_impl(nv_host, false); }
+extern "C" int sherf_importance_count(int32_t* nv2_host) { return frame_count_impl(nv2_host, true); }
 
 // The frame's launches, enqueued one by one on the three streams (with g_frame_mu held).  sherf_render_frame below either calls this, or captures
 // what it enqueues into a hipGraph once and replays the graph from then on.
@@ -176,8 +185,9 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                 SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_cnt, hipEventDisableTiming));
                 for (int k = 0; k < kMaxParts; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_part[k], evf));
                 SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_mlp, evf));
-                SHERF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d.host_nv), 64, 0));
+                SHERF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d.host_nv), 128, 0));
                 for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_rep[k], hipEventDisableTiming));
+                for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_rep2[k], hipEventDisableTiming));
                 d.init = true;
             }
         }
@@ -284,6 +294,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv + 8 + slot, f->counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
             SHERF_HIP_CHECK(hipEventRecord(d.ev_rep[slot], main));
             t_rep_last[dev] = slot;
+            d.rep_fine[slot] = false;
             d.rep_seq[slot] = t_rep_seq[dev] = ++d.rep_counter;
         }
         const bool exact = (f->flags & SHERF_FRAME_EXACT_GRIDS) != 0;
@@ -508,6 +519,75 @@ extern "C" int sherf_query_field(const sherf_frame* f, const sherf_field_query* 
     std::lock_guard<std::mutex> frame_lock(g_frame_mu);
     ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
     return render_frame_enqueue(f, 3, levels, stream_main, stream_side, stream_aux, q);
+}
+
+// The two-pass (importance sampling) frame: phase 1 of the frame as any frame's, then -- all on the caller's stream, behind the coarse network -- the fine
+// depths, the fine pass on its own buffers, and the compositing over the two merged lists.  The fine pass reads what phase 1 built (cell / near lists, SMPL
+// tables, folded tables, voxel levels: main has waited for every one of them before the coarse gather) and enqueues none of it again.  Always launch by
+// launch: never captured as a graph (the draws change with every frame).
+extern "C" int sherf_render_frame_importance(const sherf_frame* f, const sherf_importance* imp, sherf_vox_level* levels, sherf_stream_t stream_main,
+                                             sherf_stream_t stream_side, sherf_stream_t stream_aux) {
+    SHERF_CHECK_ARG(imp && imp->depths_fine && imp->points && imp->counters && imp->ray_base && imp->ray_cnt && imp->cs_idx && imp->cs_vid);
+    SHERF_CHECK_ARG(imp->cs_xs && imp->dense_vid && imp->ray_mask && imp->scan_ws && imp->geom && imp->cs_tvid && imp->tokens && imp->extras && imp->sample_out);
+    SHERF_RUN(check_frame_call(f, 3, levels, stream_main, stream_side, stream_aux));
+    SHERF_CHECK_ARG(imp->n >= 1 && imp->n <= 256 && f->S >= 3 && f->S <= 256 && f->R > 0 && f->capacity > 0 && f->vox_plan);
+    SHERF_CHECK_ARG(f->ray_o && f->ray_d && f->near && f->far && f->rgb && f->depth && f->acc);
+    const int64_t np = (int64_t)f->R * imp->n;
+    SHERF_CHECK_ARG(np < 2147483648LL && imp->capacity >= np);
+    std::lock_guard<std::mutex> frame_lock(g_frame_mu);
+    {
+        // the profiling ring's fields describe a one-pass frame (its slot is closed by phase 2, which this driver never runs): refused, not half recorded
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (g_prof_on) {
+            snprintf(g_sherf_err, sizeof(g_sherf_err), "sherf_render_frame_importance: frames are being profiled (sherf_profile_frames): not for importance frames");
+            return SHERF_EINVAL;
+        }
+    }
+    ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
+    ++g_graph_stats[2];
+    SHERF_RUN(render_frame_enqueue(f, 1, levels, stream_main, stream_side, stream_aux));
+    const int64_t tok_cap = (f->tok_capacity > 0 && f->tok_capacity < f->capacity) ? f->tok_capacity : f->capacity;
+    const int64_t ftok = (imp->tok_capacity > 0 && imp->tok_capacity < imp->capacity) ? imp->tok_capacity : imp->capacity;
+    hipStream_t main = as_stream(stream_main);
+    if (imp->u)
+        SHERF_RUN(sherf_importance_depths(f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->white_back,
+                                          tok_cap, imp->u, imp->n, imp->depths_fine, imp->points, stream_main));
+    else        // depths handed in (the tests pin the fine pass to recorded depths)
+        SHERF_RUN(sherf_importance_points(f->ray_o, f->ray_d, imp->depths_fine, f->R, imp->n, imp->points, stream_main));
+    // ---- the fine pass: renderer.py:307-368 on the fine samples ----
+    SHERF_RUN(sherf_points_mask_nn_impl(imp->points, np, f->Rg, f->Th, f->grid_hdr, f->cell_start, f->cell_pts, f->near_mask, imp->capacity, imp->counters,
+                                        imp->ray_base, imp->ray_cnt, imp->cs_idx, imp->cs_vid, imp->cs_xs, imp->dense_vid, imp->ray_mask, imp->scan_ws,
+                                        (f->near_hdr && f->near_list) ? f->near_hdr : nullptr, (f->near_hdr && f->near_list) ? f->near_list : nullptr,
+                                        stream_main, nullptr));
+    if (f->flags & SHERF_FRAME_REPORT_COUNT) {
+        int dev = 0;
+        SHERF_HIP_CHECK(hipGetDevice(&dev));
+        DevState& d = g_dev[dev];
+        const int slot = t_rep_last[dev];                   // (phase 1 took it just now, under the same lock)
+        SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv + 16 + slot, imp->counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
+        SHERF_HIP_CHECK(hipEventRecord(d.ev_rep2[slot], main));
+        d.rep_fine[slot] = true;
+    }
+    const int V = SHERF_V;
+    const size_t ncell1 = (size_t)SHERF_MAX_CELLS + 1;
+    // cs_idx holds point indices r n + j: the warp's `cs_idx / S` with S = n is the ray
+    SHERF_RUN(sherf_warp_geom_impl(imp->counters, imp->cs_idx, imp->cs_vid, imp->cs_xs, f->ray_d, imp->n, f->Rg, f->T2C, f->C2S, f->tverts,
+                                   f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, ftok, imp->geom, imp->cs_tvid, stream_main));
+    const int half_tables = (f->flags & SHERF_FRAME_HALF_TABLES) ? 1 : 0;
+    const int gv = ((f->gather_split & 2) ? 4 : 0) | ((f->gather_split & 4) ? 12 : 0) | (half_tables ? 16 : 0);
+    SHERF_RUN(sherf_gather_tokens(imp->counters, imp->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W, levels, f->tok_bias, f->bounds,
+                                  f->vox_min, f->vox_sh, 0 | gv, ftok, imp->tokens, imp->extras, stream_main));
+    if (f->mlp_prec & SHERF_MLP_OSG_DECODER)
+        SHERF_RUN(sherf_osg_decoder(imp->counters, imp->tokens, imp->extras, static_cast<const float*>(f->wstream), (f->mlp_prec & SHERF_MLP_NO_TRANSFORMER) ? 1 : 0,
+                                    ftok, imp->sample_out, stream_main));
+    else if ((f->mlp_prec & 255) != 1 && (f->flags & SHERF_FRAME_MLP_PIPELINED))
+        SHERF_RUN(sherf_nerf_mlp3(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
+    else if ((f->mlp_prec & 255) != 1 && (f->flags & SHERF_FRAME_MLP_TWO_TILES))
+        SHERF_RUN(sherf_nerf_mlp2(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
+    else
+        SHERF_RUN(sherf_nerf_mlp(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
+    return sherf_composite_merged(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, tok_cap, imp->depths_fine, imp->ray_mask, imp->ray_base,
+                                  imp->sample_out, ftok, f->ray_d, f->near, f->far, f->R, f->S, imp->n, f->white_back, f->rgb, f->depth, f->acc, stream_main);
 }
 
 extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,

@@ -1143,6 +1143,10 @@ class ImportanceRenderer(nn.Module):
     # ---- forward -----------------------------------------------------------------------------
     def forward(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
                 decoder, ray_origins, ray_directions, near, far, input_data, rendering_options):
+        n_imp = int(rendering_options.get('depth_resolution_importance', 0) or 0)
+        if n_imp != 0 and ((getattr(self, 'enable_autograd', False) and torch.is_grad_enabled()) or getattr(self, '_in_autograd', False)):
+            raise NotImplementedError('depth_resolution_importance > 0 in a grad-recorded forward (enable_autograd with grad enabled): the backward through '
+                                      'the fine samples is not built; render under torch.no_grad() or train with depth_resolution_importance = 0')
         if getattr(self, 'enable_autograd', False) and torch.is_grad_enabled() and not getattr(self, '_in_autograd', False):
             if not self.use_NeRF_decoder and not getattr(self, 'enable_osg_autograd', False):
                 raise NotImplementedError('the backward of the OSG path (use_NeRF_decoder=False: OSGDecoder, sherf_osg_decoder / sherf_bwd_osg_head) is staged: '
@@ -1175,8 +1179,8 @@ class ImportanceRenderer(nn.Module):
             with torch.cuda.device(ray_origins.device):
                 return self.forward(planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_smpl_vertex_mask, obs_sp_input,
                                     decoder, ray_origins, ray_directions, near, far, input_data, rendering_options)
-        if opts.get('depth_resolution_importance', 0) != 0:
-            raise NotImplementedError('importance sampling is unreachable/broken in the reference (renderer.py:376,383)')
+        if n_imp != 0:
+            self._check_importance(opts, n_imp, ray_origins.shape[1])
         if opts.get('disparity_space_sampling', False):
             raise NotImplementedError('only disparity_space_sampling=False (train.py:330-332)')
         _lib.composite_bits(False, opts.get('clamp_mode', 'relu'))     # 'relu' / 'softplus'; anything else: the reference marcher's assertion (ray_marcher.py:41-42)
@@ -1186,11 +1190,76 @@ class ImportanceRenderer(nn.Module):
         d['_frame_memo'] = (None, None, None)
         enc['_key_memo'] = state_key(fast_params(self.encoder_3d))
         try:
+            if n_imp != 0:                                 # the two-pass frame: inference only, nothing is recorded
+                with torch.no_grad():
+                    return self._forward(planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, decoder, ray_origins,
+                                         ray_directions, near, far, input_data, opts)
             return self._forward(planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, decoder, ray_origins,
                                  ray_directions, near, far, input_data, opts)
         finally:
             d['_frame_memo'] = None
             enc['_key_memo'] = None
+
+    # ---- importance sampling (depth_resolution_importance = N > 0): csrc/importance.hip, csrc/frame.hip: sherf_render_frame_importance ----
+    def _check_importance(self, opts, N, R):
+        """What the two-pass frame refuses, each by the option's name, before anything is enqueued."""
+        S = int(opts['depth_resolution'])
+        if N < 1 or N > 256:
+            raise ValueError(f'depth_resolution_importance must be within 0..256, got {N}')
+        if S < 3 or S > 256:
+            raise ValueError(f'depth_resolution must be within 3..256 when depth_resolution_importance > 0, got {S} '
+                             '(2 coarse samples leave weights[:, 1:-1] empty in the reference)')
+        if float(opts.get('density_noise', 0) or 0) > 0:
+            raise NotImplementedError('density_noise > 0 with depth_resolution_importance > 0 is not built (the noise is a training option; the two-pass frame is inference only)')
+        if opts.get('depth_range') is not None:
+            raise NotImplementedError('depth_range (the ray-tile sharding of sherf_amd.dist) with depth_resolution_importance > 0 is not built')
+        u = opts.get('importance_u')
+        if u is not None:
+            if not torch.is_tensor(u) or u.dtype != torch.float32 or tuple(u.shape) not in ((R, N), (1, R, N)):
+                raise ValueError(f'importance_u must be a float32 tensor of shape [{R}, {N}] or [1, {R}, {N}], got '
+                                 f'{tuple(u.shape) if torch.is_tensor(u) else type(u).__name__}' + (f' of {u.dtype}' if torch.is_tensor(u) else ''))
+            if not bool(((u >= 0) & (u <= 1)).all()):      # (NaN fails both comparisons)
+                raise ValueError('importance_u must lie within [0, 1]')
+
+    def _importance_workspace(self, wsp, R, N, dev):
+        """The fine pass's own buffers, kept in the frame's workspace (dropped with it when the frame's shape changes): the point sampler's for R * N points
+        laid out as rows of 64 and the fine depths / positions; the token side is sized by `_importance_tokens`."""
+        fw = wsp.t.get('fine')
+        if fw is not None and fw['key'] == (R, N):
+            return fw
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        rows = (R * N + 63) // 64
+        cap = rows * 64
+        fw = dict(key=(R, N), rows=rows, capacity=cap, tok_cap=0,
+                  counters=torch.zeros(8, **i32), ray_base=torch.zeros(rows, **i32), ray_cnt=torch.zeros(rows, **i32), cs_idx=torch.zeros(cap, **i32),
+                  cs_vid=torch.zeros(cap, **i32), cs_xs=torch.zeros(cap, 4, **f32), dense_vid=torch.zeros(cap, **i32),
+                  ray_mask=torch.zeros(rows, dtype=torch.int64, device=dev), scan_ws=torch.zeros(rows + rows // 1024 + 2, **i32),
+                  depths_fine=torch.zeros(R, N, **f32), points=torch.zeros(cap, 3, **f32))
+        wsp.t['fine'] = fw
+        return fw
+
+    @staticmethod
+    def _importance_tokens(fw, tok_cap, dev):
+        """The fine pass's token-side buffers (what _Workspace.tokens holds for the coarse pass) for `tok_cap` samples."""
+        if tok_cap == fw['tok_cap']:
+            return
+        f32 = dict(dtype=torch.float32, device=dev)
+        tiles = (tok_cap + 31) // 32 + 8
+        for k in ('geom', 'tokens', 'extras', 'sample_out', 'cs_tvid'):
+            fw.pop(k, None)
+        fw.update(geom=torch.zeros(tok_cap, 8, **f32), tokens=torch.zeros(tiles * 3 * 8 * 32 * 4, **f32), extras=torch.zeros(tiles * 12 * 32, **f32),
+                  sample_out=torch.zeros(tok_cap, 4, **f32), cs_tvid=torch.zeros(tok_cap, dtype=torch.int32, device=dev), tok_cap=tok_cap)
+
+    def _importance_descriptor(self, fw, u, N):
+        A = _lib.addr
+        im = _lib.Importance()
+        im.n, im.u, im.depths_fine, im.points = N, (None if u is None else A(u)), A(fw['depths_fine']), A(fw['points'])
+        im.capacity, im.tok_capacity = fw['capacity'], fw['tok_cap']
+        for k in ('counters', 'ray_base', 'ray_cnt', 'cs_idx', 'cs_vid', 'cs_xs', 'dense_vid', 'ray_mask', 'scan_ws', 'geom', 'cs_tvid', 'tokens', 'extras',
+                  'sample_out'):
+            setattr(im, k, A(fw[k]))
+        return im
 
     def _forward(self, planes, obs_input_img, obs_input_feature, canonical_sp_conv_volume, obs_sp_input, decoder, ray_origins,
                  ray_directions, near, far, input_data, opts):
@@ -1288,8 +1357,37 @@ class ImportanceRenderer(nn.Module):
         if calibrate and noise == 0:
             decide = self._calibrate(fr, decoder, dev, ws, levels, (s_main, s_side, s_aux), exact)
         rng = opts.get('depth_range')                                    # sherf_amd.dist: [lo, hi] of the WHOLE frame's depths
+        # depth_resolution_importance = N > 0: the two-pass frame (one native call: coarse phase 1, the fine depths, the fine pass on its own buffers, the
+        # merged compositing).  The draws: rendering option `importance_u`, else torch.rand from the global generator -- where sample_pdf draws them.
+        n_imp = int(opts.get('depth_resolution_importance', 0) or 0)
+        fw = im = imp_u = None
+        if n_imp > 0:
+            fw = self._importance_workspace(wsp, R, n_imp, dev)
+            given = opts.get('importance_depths')                        # TEST ONLY: the fine depths [R, N] themselves (ascending per ray) instead of draws
+            if given is not None:
+                fw['depths_fine'].copy_(given.reshape(R, n_imp))
+                imp_u = None
+            else:
+                imp_u = opts.get('importance_u')
+                imp_u = torch.rand(R, n_imp, device=dev) if imp_u is None else imp_u.reshape(R, n_imp).contiguous()
+                keep.append(imp_u)
+            # the fine token buffers follow the frame's token_capacity policy on their OWN count: 'worst' = a row per fine sample, a number as given,
+            # 'auto' = what the workspace's last importance frame needed (a first frame starts small and is rendered again once its count is known)
+            want = opts.get('token_capacity', getattr(self, 'token_capacity', 'auto'))
+            ftok = fw['capacity'] if want in ('worst', None) else (fw['tok_cap'] or self._round_tokens(0, fw['capacity'])) if want == 'auto' \
+                else self._round_tokens(int(want), fw['capacity'])
+            if ftok != fw['tok_cap']:
+                if dev.type == 'cuda' and fw['counters'].device.type == 'cuda':
+                    torch.cuda.synchronize(dev)
+                self._importance_tokens(fw, ftok, dev)
+            im = self._importance_descriptor(fw, imp_u, n_imp)
+            fr.flags |= 16                                               # SHERF_FRAME_REPORT_COUNT: both counts are checked behind the fine pass's sampler
+            verify = False                                               # (the check below covers the coarse count as well)
 
         def enqueue():
+            if im is not None:
+                _lib.call('sherf_render_frame_importance', _ct.byref(fr), _ct.byref(im), levels, s_main, s_side, s_aux)
+                return
             if noise > 0 or rng is not None:
                 _lib.call('sherf_render_frame', _ct.byref(fr), 1, levels, s_main, s_side, s_aux)
                 if noise > 0:                                            # renderer.py:435-436 (training only)
@@ -1325,6 +1423,42 @@ class ImportanceRenderer(nn.Module):
                     decide = None
                     self._wcache['auto'] = None
                 enqueue()
+        imp_counts = None
+        if im is not None:
+            # either list may hold more valid samples than its token buffers: re-size from the frame's own counts and render again.  The coarse count does
+            # not depend on the capacities; the fine count does on the COARSE one (a ray whose coarse samples lie beyond it is resampled as empty), so the
+            # worst sequence is coarse grows -> fine grows -> fits: three renders.  Every render's counts are checked; one that still does not fit fails loudly.
+            # The caller never gets the overflow NaN.
+            nv2 = (_ct.c_int32 * 2)()
+            for attempt in range(4):
+                _lib.call('sherf_importance_count', nv2)                 # waits for the fine pass's sampler only
+                grow_c, grow_f = nv2[0] > wsp.tok_cap, nv2[1] > fw['tok_cap']
+                if not (grow_c or grow_f):
+                    break
+                if attempt == 3:
+                    raise RuntimeError(f'sherf_amd: the importance frame still overflows its token buffers after three re-sizes (coarse {nv2[0]} of {wsp.tok_cap}, '
+                                       f"fine {nv2[1]} of {fw['tok_cap']})")
+                if dev.type == 'cuda' and ws['counters'].device.type == 'cuda':
+                    torch.cuda.synchronize(dev)
+                st = self.__dict__.setdefault('_flags', dict(ring=[], tripped=0))
+                if grow_c:
+                    wsp.tokens(self._round_tokens(self.TOKEN_HEADROOM * nv2[0], cap), dev)
+                    wsp.nv_sized_for = int(nv2[0])
+                    fr.tok_capacity = wsp.tok_cap
+                    if fr.zfrag:
+                        fr.zfrag = _lib.addr(wsp.zfrag(int(fr.tok_capacity), cfg[0], dev))
+                    if fr.flags & 128:
+                        fr.pefrag = _lib.addr(wsp.pefrag(dev))
+                    st['token_rerenders'] = st.get('token_rerenders', 0) + 1
+                    if decide is not None:
+                        decide = None
+                        self._wcache['auto'] = None
+                if grow_f:
+                    self._importance_tokens(fw, self._round_tokens(self.TOKEN_HEADROOM * nv2[1], fw['capacity']), dev)
+                    st['fine_token_rerenders'] = st.get('fine_token_rerenders', 0) + 1
+                im = self._importance_descriptor(fw, imp_u, n_imp)
+                enqueue()
+            imp_counts = (int(nv2[0]), int(nv2[1]))
         if want_reuse:
             if not reused:
                 wsp.obs_levels, wsp.obs_refs = levels, obs_refs
@@ -1334,7 +1468,7 @@ class ImportanceRenderer(nn.Module):
         if static_out:
             out = out.clone()
         if self.__dict__.get('_form_auto') and not calibrate and noise == 0 and self._form_key(dev, cfg[0], fr) not in self._FORM_CHOICE and cfg[0] != 'f16x3' \
-                and not (fr.flags & 8) and int(fr.mlp_parts) <= 1 and rng is None:
+                and not (fr.flags & 8) and int(fr.mlp_parts) <= 1 and rng is None and im is None:
             self._tune_mlp_form(fr, ws, dev, cfg[0], levels, (s_main, s_side, s_aux))    # (the frame above is complete and correct; the forms are timed behind it)
         ws['rgb'], ws['depth'], ws['acc'] = out[:3 * R].view(R, 3), out[3 * R:4 * R], out[4 * R:]
         # BatchNorm running statistics.  A grad-recorded forward follows the reference, which runs encoder_3d only under `if self.use_3d_feature`
@@ -1356,6 +1490,8 @@ class ImportanceRenderer(nn.Module):
                                   coord=vcoord, H=H, W=W, white_back=bool(opts.get('white_back', False)), clamp_mode=clamp_mode))
         self.last['out'] = out
         self.last['observation_reused'] = reused
+        if im is not None:
+            self.last['importance'] = dict(N=n_imp, u=imp_u, depths_fine=fw['depths_fine'], n_coarse=imp_counts[0], n_fine=imp_counts[1], ws=fw, cap=fw['tok_cap'])
         return ws['rgb'].view(1, R, 3), ws['depth'].view(1, R, 1), ws['acc'].view(1, R, 1)
 
 
