@@ -22,12 +22,16 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 EXTRA_FLAGS = {'mlp.hip': ['-fno-slp-vectorize'], 'gather.hip': ['-fno-slp-vectorize']}
 
 
+def _headers():
+    """every csrc/*.h: common.h pulls in passes.h, so a library is stale when any of them is newer"""
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith('.h')]
+
+
 def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'),
-                                                         os.path.join(HERE, '..', 'include', 'sherf_hip.h')]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + _headers() + [os.path.join(HERE, '..', 'include', 'sherf_hip.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -63,7 +67,7 @@ SOURCES_BWD = ['bwd_dense.hip', 'bwd_gemm.hip', 'bwd_encoder.hip']
 def build_bwd(force=False, verbose=True):
     """libsherf_hip_bwd.so: the backward building blocks, include/sherf_hip_bwd.h (hand-written kernels only: the dense layers'
     GEMMs are the MFMA kernels of csrc/bwd_gemm.hip; no vendor library is linked)."""
-    deps = [os.path.join(CSRC, s) for s in SOURCES_BWD] + [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'sherf_hip_bwd.h')]
+    deps = [os.path.join(CSRC, s) for s in SOURCES_BWD] + _headers() + [os.path.join(HERE, '..', 'include', 'sherf_hip_bwd.h')]
     if not force and os.path.exists(LIB_BWD) and all(os.path.getmtime(d) <= os.path.getmtime(LIB_BWD) for d in deps):
         return LIB_BWD
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
@@ -90,7 +94,7 @@ SOURCES_OPS = ['ops_lib.hip', 'ops_bias_act.hip', 'ops_upfirdn2d.hip']
 
 def build_ops(force=False, verbose=True):
     """libsherf_hip_ops.so: bias_act / upfirdn2d for the tri-plane producers (experimental), include/sherf_hip_ops.h."""
-    deps = [os.path.join(CSRC, s) for s in SOURCES_OPS] + [os.path.join(CSRC, 'ops_common.h'), os.path.join(HERE, '..', 'include', 'sherf_hip_ops.h')]
+    deps = [os.path.join(CSRC, s) for s in SOURCES_OPS] + _headers() + [os.path.join(HERE, '..', 'include', 'sherf_hip_ops.h')]
     if not force and os.path.exists(LIB_OPS) and all(os.path.getmtime(d) <= os.path.getmtime(LIB_OPS) for d in deps):
         return LIB_OPS
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -240,3 +240,5 @@ __device__ __forceinline__ void sherf_part_range(int64_t n_tiles, int part, int 
     if (hi > n_tiles) hi = n_tiles;
     if (lo > hi) lo = hi;
 }
+
+#include "passes.h"     // a frame's sample pass: its two structs, the cross-file internals, the marcher's shared arithmetic

@@ -20,30 +20,7 @@
 
 namespace {
 
-enum { CLAMP_RELU = 0, CLAMP_SOFTPLUS = 1 };
-
-// the density activation of ray_marcher.py:37-40
-template <int MODE>
-__device__ __forceinline__ float density(float sigma) {
-    if (MODE == CLAMP_RELU) return fmaxf(sigma, 0.f);
-    const float x = sigma - 1.f;
-    return x > 20.f ? x : log1pf(expf(x));
-}
-
-// d density / d sigma (threshold_backward / softplus_backward)
-template <int MODE>
-__device__ __forceinline__ float density_grad(float sigma) {
-    if (MODE == CLAMP_RELU) return sigma > 0.f ? 1.f : 0.f;
-    const float x = sigma - 1.f;
-    const float z = expf(x);
-    return x > 20.f ? 1.f : z / (z + 1.f);
-}
-
-__device__ __forceinline__ float depth_at(float near, float range, int k, int S) {
-    float step = __fdiv_rn((float)k, (float)(S - 1));
-    return __fadd_rn(near, __fmul_rn(step, range));
-}
-
+// (density<MODE>, density_grad<MODE>, depth_at and the CLAMP_* modes: csrc/passes.h, shared with the sampler and the importance depths)
 template <int BATCH, int MODE>
 __global__ void __launch_bounds__(256) composite_compact_kernel(const int32_t* __restrict__ counters,
                                                                 const int32_t* __restrict__ ray_base,

@@ -11,15 +11,6 @@
 //                   row's mask word and base, one pass, no separate fill.
 #include "common.h"
 
-int sherf_points_begin_impl(int32_t* counters, int32_t* scan_ws, int rows, int32_t* sticky, sherf_stream_t stream);                        // sample.hip
-int sherf_points_search_impl(int rows, const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const float* cand_list, int64_t list_cap,
-                             int32_t* counters, int32_t* ray_cnt, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
-                             const uint16_t* near_list, sherf_stream_t stream);                                                            // sample.hip
-int sherf_points_mask_nn_impl(const float* points, int64_t n, const float* Rg, const float* Th, const float* grid_hdr, const int32_t* cell_start,
-                              const float* cell_pts, const uint32_t* near_mask, int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt,
-                              int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
-                              const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky);
-
 namespace {
 
 constexpr int kMarkRows = 4;          // rows in flight per wave of the mark pass (cand_mark_kernel: kMarkRays)
@@ -138,24 +129,20 @@ __global__ void __launch_bounds__(256) field_scatter_kernel(const uint64_t* __re
 
 }  // namespace
 
-int sherf_points_mask_nn_impl(const float* points, int64_t n, const float* Rg, const float* Th, const float* grid_hdr, const int32_t* cell_start,
-                              const float* cell_pts, const uint32_t* near_mask, int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt,
-                              int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
-                              const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky) {
-    SHERF_CHECK_ARG(points && Rg && Th && grid_hdr && cell_start && cell_pts && near_mask);
-    SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && cs_vid && cs_xs && dense_vid && ray_mask && scan_ws);
-    SHERF_CHECK_ARG(n > 0 && n < 2147483648LL && capacity > 0 && (near_hdr == nullptr) == (near_list == nullptr));
-    SHERF_CHECK_ARG(capacity >= n);                     // (cs_xs doubles as the candidate list: it must hold a record per point)
+int sherf_points_mask_nn_impl(const float* points, int64_t n, const SherfBodyIndex& bi, const SherfSamples& s, sherf_stream_t stream, int32_t* sticky) {
+    SHERF_CHECK_ARG(points && bi.Rg && bi.Th && bi.grid_hdr && bi.cell_start && bi.cell_pts && bi.near_mask);
+    SHERF_CHECK_ARG(s.counters && s.ray_base && s.ray_cnt && s.cs_idx && s.cs_vid && s.cs_xs && s.dense_vid && s.ray_mask && s.scan_ws);
+    SHERF_CHECK_ARG(n > 0 && n < 2147483648LL && s.capacity > 0 && (bi.near_hdr == nullptr) == (bi.near_list == nullptr));
+    SHERF_CHECK_ARG(s.capacity >= n);                   // (cs_xs doubles as the candidate list: it must hold a record per point)
     hipStream_t st = as_stream(stream);
     const int rows = (int)((n + 63) / 64);
-    const SherfScanWs w = sherf_scan_ws(scan_ws, rows);
-    SHERF_RUN(sherf_points_begin_impl(counters, scan_ws, rows, sticky, stream));
-    hipLaunchKernelGGL(point_mark_kernel, dim3(cdiv(rows, kRowsPerWg)), dim3(256), 0, st, points, n, rows, Rg, Th, grid_hdr, near_mask,
-                       reinterpret_cast<float4*>(cs_xs), capacity, w.cand_count, ray_mask, g_sherf_debug);
-    SHERF_RUN(sherf_points_search_impl(rows, grid_hdr, cell_start, cell_pts, cs_xs, capacity, counters, ray_cnt, dense_vid, ray_mask, scan_ws, near_hdr,
-                                       near_list, stream));
-    hipLaunchKernelGGL(compact_points_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, points, rows, Rg, Th, w.base_local, w.chunk_sum, ray_mask, dense_vid,
-                       capacity, ray_base, cs_idx, cs_vid, reinterpret_cast<float4*>(cs_xs));
+    const SherfScanWs w = sherf_scan_ws(s.scan_ws, rows);
+    SHERF_RUN(sherf_points_begin_impl(s.counters, s.scan_ws, rows, sticky, stream));
+    hipLaunchKernelGGL(point_mark_kernel, dim3(cdiv(rows, kRowsPerWg)), dim3(256), 0, st, points, n, rows, bi.Rg, bi.Th, bi.grid_hdr, bi.near_mask,
+                       reinterpret_cast<float4*>(s.cs_xs), s.capacity, w.cand_count, s.ray_mask, g_sherf_debug);
+    SHERF_RUN(sherf_points_search_impl(rows, bi, s, stream));
+    hipLaunchKernelGGL(compact_points_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, points, rows, bi.Rg, bi.Th, w.base_local, w.chunk_sum, s.ray_mask, s.dense_vid,
+                       s.capacity, s.ray_base, s.cs_idx, s.cs_vid, reinterpret_cast<float4*>(s.cs_xs));
     SHERF_LAUNCH_CHECK();
 }
 
@@ -163,8 +150,8 @@ extern "C" int sherf_points_mask_nn(const float* points, int64_t n, const float*
                                     const float* cell_pts, const uint32_t* near_mask, int64_t capacity, int32_t* counters, int32_t* ray_base,
                                     int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
                                     int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream) {
-    return sherf_points_mask_nn_impl(points, n, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt, cs_idx, cs_vid, cs_xs,
-                                     dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr);
+    return sherf_points_mask_nn_impl(points, n, {Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, near_hdr, near_list},
+                                     {counters, ray_base, ray_cnt, cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, capacity}, stream, nullptr);
 }
 
 extern "C" int sherf_field_scatter(int32_t* counters, const uint64_t* ray_mask, const int32_t* ray_base, const float* sample_out, int64_t n, int64_t tok_cap,

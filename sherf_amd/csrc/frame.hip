@@ -13,22 +13,6 @@
 #include <functional>
 #include <mutex>
 
-int sherf_svox_encode_impl(const sherf_svox_plan* p, const int32_t* coord, const float* feat, int n, int training,
-                           sherf_vox_level* levels_out_host, sherf_stream_t stream, hipEvent_t ev, int ev_layer,
-                           sherf_stream_t aux, hipEvent_t* lev_ev, const std::function<int()>* after_levels, int fold_half);   // svox.hip
-int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const float* near, const float* far, int R, int S, const float* Rg, const float* Th,
-                              const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
-                              int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
-                              uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream,
-                              int32_t* sticky, int32_t* cell_ws, int64_t cell_ws_len);                                          // sample.hip
-int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
-                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
-                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);                               // sample.hip
-int sherf_points_mask_nn_impl(const float* points, int64_t n, const float* Rg, const float* Th, const float* grid_hdr, const int32_t* cell_start,
-                              const float* cell_pts, const uint32_t* near_mask, int64_t capacity, int32_t* counters, int32_t* ray_base, int32_t* ray_cnt,
-                              int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
-                              const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky);                               // field.hip
-
 namespace {
 
 constexpr int kMaxDev = 16;
@@ -107,13 +91,39 @@ extern "C" int sherf_profile_frames_read(float* ms_host, int32_t max_n, int32_t*
     return SHERF_OK;
 }
 
+// The current device and its state.  `create`: with its events and pinned words, which a device's first frame makes; else d->init tells whether one has.
+static int device_state(int& dev, DevState*& d, bool create) {
+    SHERF_HIP_CHECK(hipGetDevice(&dev));
+    SHERF_CHECK_ARG(dev >= 0 && dev < kMaxDev);
+    d = &g_dev[dev];
+    if (!create) return SHERF_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (d->init) return SHERF_OK;
+    // (device-to-device events; the two the HOST waits on -- ev_cnt, ev_rep -- keep the default system-scope release)
+    const unsigned evf = hipEventDisableTiming | ((sherf_experiment() & 4) ? hipEventReleaseToDevice : 0u);
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_start, evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_smpl, evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_enc, evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_mid, evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_fold, evf));
+    for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_lev[k], evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_cnt, hipEventDisableTiming));
+    for (int k = 0; k < kMaxParts; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_part[k], evf));
+    SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_mlp, evf));
+    SHERF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d->host_nv), 128, 0));
+    for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_rep[k], hipEventDisableTiming));
+    for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d->ev_rep2[k], hipEventDisableTiming));
+    d->init = true;
+    return SHERF_OK;
+}
+
 // `fine`: the importance frame's second pair of the slot -> nv_host[0..1] = {coarse, fine}
 static int frame_count_impl(int32_t* nv_host, bool fine) {
     SHERF_CHECK_ARG(nv_host);
     int dev = 0;
-    SHERF_HIP_CHECK(hipGetDevice(&dev));
-    SHERF_CHECK_ARG(dev >= 0 && dev < kMaxDev);
-    DevState& d = g_dev[dev];
+    DevState* dp = nullptr;
+    SHERF_RUN(device_state(dev, dp, false));
+    DevState& d = *dp;
     const int slot = t_rep_last[dev];
     hipEvent_t ev;
     auto overtaken = [&]() -> int {
@@ -141,6 +151,77 @@ static int frame_count_impl(int32_t* nv_host, bool fine) {
 extern "C" int sherf_frame_count(int32_t* nv_host) { return frame_count_impl(nv_host, false); }
 extern "C" int sherf_importance_count(int32_t* nv2_host) { return frame_count_impl(nv2_host, true); }
 
+// ---- the pieces of a frame that more than one driver below enqueues; a pass's buffers come as samples(*frame) or samples(*importance) ----
+
+// main: cell lists, near lists, a4-a6 sampling / mask / nearest vertex / compaction into the frame's own buffers.  `after_cells`: an event main waits for
+// between the cell lists and the near lists (the staggered start), or NULL.  `q`: the point sampler in the ray sampler's place.
+static int enqueue_index_and_sampler(const sherf_frame* f, const sherf_field_query* q, sherf_stream_t stream_main, hipEvent_t after_cells) {
+    const SherfBodyIndex bi = body_index(*f);
+    SHERF_RUN(sherf_build_cells2(f->verts, f->Rg, f->Th, f->tverts, SHERF_V, 0.05f, f->grid_hdr, f->cell_start, f->cell_pts,
+                                 f->cell_scratch, bi.near_list ? nullptr : f->near_mask, stream_main));
+    if (after_cells) SHERF_HIP_CHECK(hipStreamWaitEvent(as_stream(stream_main), after_cells, 0));
+    SHERF_CAP_TRACE("near lists");
+    if (bi.near_list)
+        SHERF_RUN(sherf_build_near_lists(f->grid_hdr, f->cell_pts, SHERF_V, 0.05f, f->near_hdr, f->near_list, f->near_list_cap, f->near_mask, stream_main));
+    SHERF_CAP_TRACE("sampler");
+    if (q) return sherf_points_mask_nn_impl(q->points, q->n, bi, samples(*f), stream_main, f->sticky);
+    return sherf_sample_mask_nn_impl({f->ray_o, f->ray_d, f->near, f->far, f->R, f->S}, bi, samples(*f), stream_main, f->sticky, f->cell_ws, f->cell_ws_len);
+}
+
+// SHERF_FRAME_REPORT_COUNT: a pass's valid-sample count copied to a slot's pinned word right behind the pass's sampler (g_frame_mu held).  The coarse pass
+// takes the device's next slot for the calling thread; the fine pass of an importance frame fills the second pair of the slot its phase 1 took just now,
+// under the same lock.
+static int report_count(DevState& d, int dev, const int32_t* counters, bool fine, hipStream_t main) {
+    const int slot = fine ? t_rep_last[dev] : d.rep_next;
+    if (!fine) d.rep_next = (d.rep_next + 1) % 8;
+    SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv + (fine ? 16 : 8) + slot, counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
+    SHERF_HIP_CHECK(hipEventRecord(fine ? d.ev_rep2[slot] : d.ev_rep[slot], main));
+    d.rep_fine[slot] = fine;
+    if (!fine) {
+        t_rep_last[dev] = slot;
+        d.rep_seq[slot] = t_rep_seq[dev] = ++d.rep_counter;
+    }
+    return SHERF_OK;
+}
+
+// a8-a10: the warp of a pass's first s.tok_cap samples against the frame's second cell list, the target-pose vertices'
+static int enqueue_warp(const sherf_frame* f, const SherfSamples& s, const float* dirs, int dir_stride, sherf_stream_t stream) {
+    SherfBodyIndex target = {};
+    target.Rg = f->Rg; target.grid_hdr = f->grid_hdr + kGridHdr; target.cell_start = f->cell_start + ((size_t)SHERF_MAX_CELLS + 1);
+    target.cell_pts = f->cell_pts + (size_t)SHERF_V * 4;
+    return sherf_warp_geom_impl(target, f->T2C, f->C2S, f->tverts, s, stream, dirs, dir_stride);
+}
+
+// the gather's mode word without its pass bits.  gather_split bit 1: branchless voxel-row loads (mode | 4); bit 2: in 128 VGPRs (mode | 12); mode | 16: fp16 tables
+static int gather_mode(const sherf_frame* f) {
+    return ((f->gather_split & 2) ? 4 : 0) | ((f->gather_split & 4) ? 12 : 0) | ((f->flags & SHERF_FRAME_HALF_TABLES) ? 16 : 0);
+}
+
+// a10-a12: one gather launch of a pass (`levels` may be NULL for the pass without voxel taps; `pe`: sherf_gather_tokens_pe, into f->pefrag too)
+static int enqueue_gather(const sherf_frame* f, const SherfSamples& s, const sherf_vox_level* levels, int mode, bool pe, sherf_stream_t stream) {
+    if (pe)
+        return sherf_gather_tokens_pe(s.counters, s.geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W, levels, f->tok_bias, f->bounds,
+                                      f->vox_min, f->vox_sh, mode, s.tok_cap, s.tokens, s.extras, f->pefrag, stream);
+    return sherf_gather_tokens(s.counters, s.geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W, levels, f->tok_bias, f->bounds,
+                               f->vox_min, f->vox_sh, mode, s.tok_cap, s.tokens, s.extras, stream);
+}
+
+// a13-a14: the per-sample network of a pass in ONE launch (or the split form's two), in the form the frame's flags select.  `pe_frags` / `split`: the forms
+// only the coarse pass takes; `dbg`: the debug word whose bits 25 / 24 flip the pipelined / two-tile form for A/B runs -- the coarse pass's, 0 for a fine pass.
+static int enqueue_network(const sherf_frame* f, const SherfSamples& s, bool pe_frags, bool split, int dbg, sherf_stream_t stream) {
+    const bool single = (f->mlp_prec & 255) != 1;
+    if (f->mlp_prec & SHERF_MLP_OSG_DECODER)
+        return sherf_osg_decoder(s.counters, s.tokens, s.extras, static_cast<const float*>(f->wstream), (f->mlp_prec & SHERF_MLP_NO_TRANSFORMER) ? 1 : 0, s.tok_cap,
+                                 s.sample_out, stream);
+    if (pe_frags) return sherf_nerf_mlp3_pe(s.counters, s.tokens, s.extras, f->pefrag, f->wstream, f->wbias, f->mlp_prec, s.tok_cap, s.sample_out, stream);
+    if (split) return sherf_nerf_mlp_split(s.counters, s.tokens, s.extras, f->wstream, f->wbias, f->mlp_prec, s.tok_cap, f->zfrag, s.sample_out, stream);
+    if (single && (((f->flags & SHERF_FRAME_MLP_PIPELINED) != 0) != ((dbg & (1 << 25)) != 0)))
+        return sherf_nerf_mlp3(s.counters, s.tokens, s.extras, f->wstream, f->wbias, f->mlp_prec, s.tok_cap, s.sample_out, stream);
+    if (single && (((f->flags & SHERF_FRAME_MLP_TWO_TILES) != 0) != ((dbg & (1 << 24)) != 0)))
+        return sherf_nerf_mlp2(s.counters, s.tokens, s.extras, f->wstream, f->wbias, f->mlp_prec, s.tok_cap, s.sample_out, stream);
+    return sherf_nerf_mlp(s.counters, s.tokens, s.extras, f->wstream, f->wbias, f->mlp_prec, s.tok_cap, s.sample_out, stream);
+}
+
 // The frame's launches, enqueued one by one on the three streams (with g_frame_mu held).  sherf_render_frame below either calls this, or captures
 // what it enqueues into a hipGraph once and replays the graph from then on.
 // `q` (sherf_query_field; NULL for a frame): the same launches with the point sampler (csrc/field.hip) in the ray sampler's place, the warp reading one view
@@ -150,47 +231,17 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
     hipStream_t main = as_stream(stream_main), side = as_stream(stream_side);
     if (phase == 4) {                                                // the sampler alone: counters[0] = the frame's valid samples
         SHERF_CHECK_ARG(f->R > 0 && f->S > 0 && f->capacity > 0);
-        const bool lists = f->near_hdr && f->near_list;
-        SHERF_RUN(sherf_build_cells2(f->verts, f->Rg, f->Th, f->tverts, SHERF_V, 0.05f, f->grid_hdr, f->cell_start, f->cell_pts,
-                                     f->cell_scratch, lists ? nullptr : f->near_mask, stream_main));
-        if (lists)
-            SHERF_RUN(sherf_build_near_lists(f->grid_hdr, f->cell_pts, SHERF_V, 0.05f, f->near_hdr, f->near_list, f->near_list_cap, f->near_mask, stream_main));
-        SHERF_RUN(sherf_sample_mask_nn_impl(f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->Rg, f->Th, f->grid_hdr, f->cell_start,
-                                       f->cell_pts, f->near_mask, f->capacity, f->counters, f->ray_base, f->ray_cnt, f->cs_idx,
-                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky,
-                                       f->cell_ws, f->cell_ws_len));
-        return SHERF_OK;
+        return enqueue_index_and_sampler(f, nullptr, stream_main, nullptr);
     }
-    // token-side capacity: what geom / tokens / extras / sample_out hold
-    const int64_t tok_cap = (f->tok_capacity > 0 && f->tok_capacity < f->capacity) ? f->tok_capacity : f->capacity;
+    const SherfSamples s = samples(*f);
     const auto host_t0 = std::chrono::steady_clock::now();
     static int cur_slot = -1;          // guarded by g_frame_mu; phase 2 of a split call reuses phase 1's slot
 #define SHERF_PROF(j, strm) do { if (cur_slot >= 0) SHERF_HIP_CHECK(hipEventRecord(g_prof_ev[cur_slot][j], strm)); } while (0)
     if (phase & 1) {
         int dev = 0;
-        SHERF_HIP_CHECK(hipGetDevice(&dev));
-        SHERF_CHECK_ARG(dev >= 0 && dev < kMaxDev);
-        DevState& d = g_dev[dev];
-        {
-            std::lock_guard<std::mutex> lk(g_mu);
-            if (!d.init) {
-                // (device-to-device events; the two the HOST waits on -- ev_cnt, ev_rep -- keep the default system-scope release)
-                const unsigned evf = hipEventDisableTiming | ((sherf_experiment() & 4) ? hipEventReleaseToDevice : 0u);
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_start, evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_smpl, evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_enc, evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_mid, evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_fold, evf));
-                for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_lev[k], evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_cnt, hipEventDisableTiming));
-                for (int k = 0; k < kMaxParts; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_part[k], evf));
-                SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_mlp, evf));
-                SHERF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d.host_nv), 128, 0));
-                for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_rep[k], hipEventDisableTiming));
-                for (int k = 0; k < 8; ++k) SHERF_HIP_CHECK(hipEventCreateWithFlags(&d.ev_rep2[k], hipEventDisableTiming));
-                d.init = true;
-            }
-        }
+        DevState* dp = nullptr;
+        SHERF_RUN(device_state(dev, dp, true));
+        DevState& d = *dp;
         SHERF_CHECK_ARG((q || (f->R > 0 && f->S > 0)) && f->capacity > 0 && f->vox_plan);
         const int V = SHERF_V;
         {
@@ -243,7 +294,6 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
                 SHERF_HIP_CHECK(hipEventRecord(d.ev_fold, as_stream(stream_aux)));
             }
         }
-        const size_t ncell1 = (size_t)SHERF_MAX_CELLS + 1;
         auto enqueue_encoder = [&]() -> int {        // ---- side: a11 sparse voxel encoder ----
             if (reuse) {
                 SHERF_PROF(2, side);                 // (the timeline's "encoder done" stays readable: right behind the frame's start)
@@ -264,23 +314,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         SHERF_CAP_TRACE("cells");
         if (encoder_first) SHERF_RUN(enqueue_encoder());
         // ---- main: cell lists, a4-a6 sampling / mask / nearest vertex / compaction, table re-layout ----
-        const bool lists = f->near_hdr && f->near_list;             // exact vertex list per near-mask sub-cell: its counts also give the mask
-        SHERF_RUN(sherf_build_cells2(f->verts, f->Rg, f->Th, f->tverts, V, 0.05f, f->grid_hdr, f->cell_start, f->cell_pts,
-                                     f->cell_scratch, lists ? nullptr : f->near_mask, stream_main));
-        if (stagger >= 0) SHERF_HIP_CHECK(hipStreamWaitEvent(main, stagger < f->vox_plan->n_layers ? d.ev_mid : d.ev_enc, 0));
-        SHERF_CAP_TRACE("near lists");
-        if (lists)
-            SHERF_RUN(sherf_build_near_lists(f->grid_hdr, f->cell_pts, V, 0.05f, f->near_hdr, f->near_list, f->near_list_cap, f->near_mask, stream_main));
-        SHERF_CAP_TRACE("sampler");
-        if (q)
-            SHERF_RUN(sherf_points_mask_nn_impl(q->points, q->n, f->Rg, f->Th, f->grid_hdr, f->cell_start, f->cell_pts, f->near_mask, f->capacity, f->counters,
-                                                f->ray_base, f->ray_cnt, f->cs_idx, f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr,
-                                                f->near_list, stream_main, f->sticky));
-        else
-        SHERF_RUN(sherf_sample_mask_nn_impl(f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->Rg, f->Th, f->grid_hdr, f->cell_start,
-                                       f->cell_pts, f->near_mask, f->capacity, f->counters, f->ray_base, f->ray_cnt, f->cs_idx,
-                                       f->cs_vid, f->cs_xs, f->dense_vid, f->ray_mask, f->scan_ws, f->near_hdr, f->near_list, stream_main, f->sticky,
-                                       f->cell_ws, f->cell_ws_len));
+        SHERF_RUN(enqueue_index_and_sampler(f, q, stream_main, stagger < 0 ? nullptr : stagger < f->vox_plan->n_layers ? d.ev_mid : d.ev_enc));
         SHERF_CAP_TRACE("sampler queued");
         // SHERF_FRAME_EXACT_GRIDS: the kernels after the compaction are launched for the frame's ACTUAL number of valid samples instead
         // of the buffers' capacity (R*S, of which a body fills a few percent: the MLP's grid is then ~96 % workgroups that allocate
@@ -288,15 +322,7 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         // copied to pinned memory here and awaited just before the warp is enqueued -- the one host synchronisation of this mode (the
         // reference synchronises at the same point: its boolean-mask indexing, renderer.py:320-321); the encoder chain and the table
         // folds are enqueued in between and keep the GPU busy meanwhile.  Same results: every kernel clamps to min(count, capacity).
-        if (f->flags & SHERF_FRAME_REPORT_COUNT) {
-            const int slot = d.rep_next;
-            d.rep_next = (d.rep_next + 1) % 8;
-            SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv + 8 + slot, f->counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
-            SHERF_HIP_CHECK(hipEventRecord(d.ev_rep[slot], main));
-            t_rep_last[dev] = slot;
-            d.rep_fine[slot] = false;
-            d.rep_seq[slot] = t_rep_seq[dev] = ++d.rep_counter;
-        }
+        if (f->flags & SHERF_FRAME_REPORT_COUNT) SHERF_RUN(report_count(d, dev, f->counters, false, main));
         const bool exact = (f->flags & SHERF_FRAME_EXACT_GRIDS) != 0;
         if (exact) {
             SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv, f->counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
@@ -309,30 +335,26 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
         // ---- main: a8-a10 warp, a10-a12 gather, a13-a14 MLP ----
         SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_smpl, 0));
         if (stream_aux && !reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_fold, 0));
-        int64_t cap = tok_cap;
+        SherfSamples run = s;           // the pass as warp, gather and network are LAUNCHED for it: run.tok_cap samples
         if (exact) {
             SHERF_HOST_STAMP(xp, "count wait begins");
             SHERF_HIP_CHECK(hipEventSynchronize(d.ev_cnt));
             SHERF_HOST_STAMP(xp, "count wait ends");
             int64_t c = *d.host_nv > 0 ? ((int64_t)*d.host_nv + 255) / 256 * 256 : 256;      // whole MLP tile groups
-            if (c < cap) cap = c;
+            if (c < run.tok_cap) run.tok_cap = c;
         }
         SHERF_CAP_TRACE("warp");
         if (q)          // cs_idx holds point indices: one direction per point
-            SHERF_RUN(sherf_warp_geom_impl(f->counters, f->cs_idx, f->cs_vid, f->cs_xs, q->dirs, 1, f->Rg, f->T2C, f->C2S, f->tverts,
-                                           f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, cap, f->geom,
-                                           f->cs_tvid, stream_main));
+            SHERF_RUN(enqueue_warp(f, run, q->dirs, 1, stream_main));
         else
-        SHERF_RUN(sherf_warp_geom(f->counters, f->cs_idx, f->cs_vid, f->cs_xs, f->ray_d, f->S, f->Rg, f->T2C, f->C2S, f->tverts,
-                                  f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, cap, f->geom,
-                                  f->cs_tvid, stream_main));
-        const int gv = ((f->gather_split & 2) ? 4 : 0) | ((f->gather_split & 4) ? 12 : 0) |  // bit 1: branchless voxel-row loads (mode | 4); bit 2: in 128 VGPRs (mode | 12)
-                       (half_tables ? 16 : 0);                                                // mode | 16: fp16 tables
+            SHERF_RUN(enqueue_warp(f, run, f->ray_d, f->S, stream_main));
+        const int gv = gather_mode(f);
         // Gather and MLP in `nparts` contiguous parts of the tile list, part k's MLP (matrix pipe) on the side stream beside part k + 1's
         // gather (texture addresser) on the main one: the two kernels are bound by different units of the CU (frame->mlp_parts).
         // SHERF_MLP_OSG_DECODER: the per-sample network is sherf_osg_decoder (csrc/osg.hip) -- one launch form, no parts, no split, no encodings from the gather
         const bool osg = (f->mlp_prec & SHERF_MLP_OSG_DECODER) != 0;
         const int nparts = osg ? 1 : std::min(((g_sherf_debug >> 16) & 15) ? ((g_sherf_debug >> 16) & 15) : f->mlp_parts, kMaxParts);   // (debug bits 16-19 override: A/B runs)
+        // debug bit 13 flips the form for A/B runs in one process (a frame without zfrag always takes the one-launch kernel)
         const bool split_form = !osg && f->zfrag && (((f->flags & SHERF_FRAME_MLP_SPLIT) != 0) != ((g_sherf_debug & 8192) != 0));
         // SHERF_FRAME_PE_FRAGS (round 6): the gather writes the positional encodings as fp16 operand fragments and the pipelined single-fp16-product
         // network reads them (sherf_gather_tokens_pe -> sherf_nerf_mlp3_pe; bit-identical frames).  Only in the configuration it is built for: fp16
@@ -343,16 +365,14 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             SHERF_PROF(3, main);
             if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
             for (int k = 0; k < nparts; ++k) {
-                SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
-                                              levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 0 | gv | (k << 8) | (nparts << 16), cap,
-                                              f->tokens, f->extras, stream_main));
+                SHERF_RUN(enqueue_gather(f, run, levels, 0 | gv | (k << 8) | (nparts << 16), false, stream_main));
                 SHERF_HIP_CHECK(hipEventRecord(d.ev_part[k], main));
                 SHERF_HIP_CHECK(hipStreamWaitEvent(side, d.ev_part[k], 0));
                 if ((f->mlp_prec & 255) != 1 && (f->flags & SHERF_FRAME_MLP_PIPELINED))       // two workgroups per CU: room for the next part's gather beside it
-                    SHERF_RUN(sherf_nerf_mlp3_part(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, k, nparts,
+                    SHERF_RUN(sherf_nerf_mlp3_part(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, run.tok_cap, f->sample_out, k, nparts,
                                                    (g_sherf_debug & (1 << 26)) ? 3 : (g_sherf_debug & (1 << 27)) ? 1 : 2, stream_side));   // (debug bits 26 / 27: residency 3 / 1, for A/B runs)
                 else
-                    SHERF_RUN(sherf_nerf_mlp_part(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, k, nparts,
+                    SHERF_RUN(sherf_nerf_mlp_part(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, run.tok_cap, f->sample_out, k, nparts,
                                                   stream_side));
             }
             SHERF_PROF(4, main);
@@ -360,57 +380,30 @@ static int render_frame_enqueue(const sherf_frame* f, int phase, sherf_vox_level
             SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_mlp, 0));
             SHERF_PROF(5, main);
         } else {
-        if (f->gather_split & 1) {      // tri-plane + pixel taps do not need the encoder: run them while it is still busy
-            SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
-                                          nullptr, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 1 | gv, cap, f->tokens,
-                                          f->extras, stream_main));
-            SHERF_PROF(3, main);
-            if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
-            SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
-                                          levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 2 | gv, cap, f->tokens,
-                                          f->extras, stream_main));
-        } else {
-            SHERF_PROF(3, main);
-            if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
-            if (pe_frags)
-                SHERF_RUN(sherf_gather_tokens_pe(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
-                                                 levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 0 | gv, cap, f->tokens,
-                                                 f->extras, f->pefrag, stream_main));
-            else
-            SHERF_RUN(sherf_gather_tokens(f->counters, f->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W,
-                                          levels, f->tok_bias, f->bounds, f->vox_min, f->vox_sh, 0 | gv, cap, f->tokens,
-                                          f->extras, stream_main));
-        }
-        SHERF_CAP_TRACE("network");
-        SHERF_PROF(4, main);
-        // debug bit 13 flips the form for A/B runs in one process (a frame without zfrag always takes the one-launch kernel)
-        const bool split = split_form;
-        if (osg)
-            SHERF_RUN(sherf_osg_decoder(f->counters, f->tokens, f->extras, static_cast<const float*>(f->wstream), (f->mlp_prec & SHERF_MLP_NO_TRANSFORMER) ? 1 : 0, cap,
-                                        f->sample_out, stream_main));
-        else if (pe_frags)
-            SHERF_RUN(sherf_nerf_mlp3_pe(f->counters, f->tokens, f->extras, f->pefrag, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, stream_main));
-        else if (split)
-            SHERF_RUN(sherf_nerf_mlp_split(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->zfrag,
-                                           f->sample_out, stream_main));
-        else if ((f->mlp_prec & 255) != 1 && (((f->flags & SHERF_FRAME_MLP_PIPELINED) != 0) != ((g_sherf_debug & (1 << 25)) != 0)))    // (debug bit 25 flips the form: A/B runs)
-            SHERF_RUN(sherf_nerf_mlp3(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, stream_main));
-        else if ((f->mlp_prec & 255) != 1 && (((f->flags & SHERF_FRAME_MLP_TWO_TILES) != 0) != ((g_sherf_debug & (1 << 24)) != 0)))   // (debug bit 24 flips the form: A/B runs)
-            SHERF_RUN(sherf_nerf_mlp2(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap, f->sample_out, stream_main));
-        else
-            SHERF_RUN(sherf_nerf_mlp(f->counters, f->tokens, f->extras, f->wstream, f->wbias, f->mlp_prec, cap,
-                                     f->sample_out, stream_main));
-        SHERF_PROF(5, main);
+            if (f->gather_split & 1) {      // tri-plane + pixel taps do not need the encoder: run them while it is still busy
+                SHERF_RUN(enqueue_gather(f, run, nullptr, 1 | gv, false, stream_main));
+                SHERF_PROF(3, main);
+                if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
+                SHERF_RUN(enqueue_gather(f, run, levels, 2 | gv, false, stream_main));
+            } else {
+                SHERF_PROF(3, main);
+                if (!reuse) SHERF_HIP_CHECK(hipStreamWaitEvent(main, d.ev_enc, 0));
+                SHERF_RUN(enqueue_gather(f, run, levels, 0 | gv, pe_frags, stream_main));
+            }
+            SHERF_CAP_TRACE("network");
+            SHERF_PROF(4, main);
+            SHERF_RUN(enqueue_network(f, run, pe_frags, split_form, g_sherf_debug, stream_main));      // (debug bits 25 / 24 flip the form: A/B runs)
+            SHERF_PROF(5, main);
         }
     }
     if (phase & 2) {
         // ---- a15-a16 ----
         SHERF_CAP_TRACE("compositing");
         if (q)          // ---- renderer.py:364-368 materialised ----
-            SHERF_RUN(sherf_field_scatter(f->counters, f->ray_mask, f->ray_base, f->sample_out, q->n, tok_cap, q->rgb, q->sigma, q->mask, stream_main));
+            SHERF_RUN(sherf_field_scatter(f->counters, f->ray_mask, f->ray_base, f->sample_out, q->n, s.tok_cap, q->rgb, q->sigma, q->mask, stream_main));
         else
-        SHERF_RUN(sherf_composite_compact_cap(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, f->ray_d, f->near, f->far,
-                                              f->R, f->S, f->white_back, tok_cap, f->rgb, f->depth, f->acc, stream_main));
+            SHERF_RUN(sherf_composite_compact_cap(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, f->ray_d, f->near, f->far,
+                                                  f->R, f->S, f->white_back, s.tok_cap, f->rgb, f->depth, f->acc, stream_main));
         SHERF_PROF(6, main);
         SHERF_HOST_STAMP(sherf_experiment(), "frame leave");
         if (cur_slot >= 0) {
@@ -509,6 +502,13 @@ static int check_frame_call(const sherf_frame* f, int phase, const sherf_vox_lev
     return SHERF_OK;
 }
 
+// a frame enqueued launch by launch, counted as such (sherf_frame_graph_stats)
+static int render_frame_eager(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main, sherf_stream_t stream_side,
+                              sherf_stream_t stream_aux) {
+    ++g_graph_stats[2];
+    return render_frame_enqueue(f, phase, levels, stream_main, stream_side, stream_aux);
+}
+
 // The field query's driver: phases 1 + 2 of a frame with the point sampler and the scatter-back (render_frame_enqueue with `q`).  Always enqueued launch by
 // launch: a query is never captured as a graph (its descriptor changes with every chunk of points).
 extern "C" int sherf_query_field(const sherf_frame* f, const sherf_field_query* q, sherf_vox_level* levels, sherf_stream_t stream_main,
@@ -544,50 +544,27 @@ extern "C" int sherf_render_frame_importance(const sherf_frame* f, const sherf_i
         }
     }
     ++g_obs_stats[(f->flags & SHERF_FRAME_REUSE_OBSERVATION) ? 1 : 0];
-    ++g_graph_stats[2];
-    SHERF_RUN(render_frame_enqueue(f, 1, levels, stream_main, stream_side, stream_aux));
-    const int64_t tok_cap = (f->tok_capacity > 0 && f->tok_capacity < f->capacity) ? f->tok_capacity : f->capacity;
-    const int64_t ftok = (imp->tok_capacity > 0 && imp->tok_capacity < imp->capacity) ? imp->tok_capacity : imp->capacity;
-    hipStream_t main = as_stream(stream_main);
+    SHERF_RUN(render_frame_eager(f, 1, levels, stream_main, stream_side, stream_aux));
+    const SherfSamples coarse = samples(*f), fine = samples(*imp);
     if (imp->u)
         SHERF_RUN(sherf_importance_depths(f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, f->ray_o, f->ray_d, f->near, f->far, f->R, f->S, f->white_back,
-                                          tok_cap, imp->u, imp->n, imp->depths_fine, imp->points, stream_main));
+                                          coarse.tok_cap, imp->u, imp->n, imp->depths_fine, imp->points, stream_main));
     else        // depths handed in (the tests pin the fine pass to recorded depths)
         SHERF_RUN(sherf_importance_points(f->ray_o, f->ray_d, imp->depths_fine, f->R, imp->n, imp->points, stream_main));
-    // ---- the fine pass: renderer.py:307-368 on the fine samples ----
-    SHERF_RUN(sherf_points_mask_nn_impl(imp->points, np, f->Rg, f->Th, f->grid_hdr, f->cell_start, f->cell_pts, f->near_mask, imp->capacity, imp->counters,
-                                        imp->ray_base, imp->ray_cnt, imp->cs_idx, imp->cs_vid, imp->cs_xs, imp->dense_vid, imp->ray_mask, imp->scan_ws,
-                                        (f->near_hdr && f->near_list) ? f->near_hdr : nullptr, (f->near_hdr && f->near_list) ? f->near_list : nullptr,
-                                        stream_main, nullptr));
+    // ---- the fine pass: renderer.py:307-368 on the fine samples; the debug flips of the launch forms act on the coarse pass only ----
+    SHERF_RUN(sherf_points_mask_nn_impl(imp->points, np, body_index(*f), fine, stream_main, nullptr));
     if (f->flags & SHERF_FRAME_REPORT_COUNT) {
         int dev = 0;
-        SHERF_HIP_CHECK(hipGetDevice(&dev));
-        DevState& d = g_dev[dev];
-        const int slot = t_rep_last[dev];                   // (phase 1 took it just now, under the same lock)
-        SHERF_HIP_CHECK(hipMemcpyAsync(d.host_nv + 16 + slot, imp->counters, sizeof(int32_t), hipMemcpyDeviceToHost, main));
-        SHERF_HIP_CHECK(hipEventRecord(d.ev_rep2[slot], main));
-        d.rep_fine[slot] = true;
+        DevState* d = nullptr;
+        SHERF_RUN(device_state(dev, d, false));
+        SHERF_RUN(report_count(*d, dev, imp->counters, true, as_stream(stream_main)));
     }
-    const int V = SHERF_V;
-    const size_t ncell1 = (size_t)SHERF_MAX_CELLS + 1;
     // cs_idx holds point indices r n + j: the warp's `cs_idx / S` with S = n is the ray
-    SHERF_RUN(sherf_warp_geom_impl(imp->counters, imp->cs_idx, imp->cs_vid, imp->cs_xs, f->ray_d, imp->n, f->Rg, f->T2C, f->C2S, f->tverts,
-                                   f->grid_hdr + kGridHdr, f->cell_start + ncell1, f->cell_pts + (size_t)V * 4, ftok, imp->geom, imp->cs_tvid, stream_main));
-    const int half_tables = (f->flags & SHERF_FRAME_HALF_TABLES) ? 1 : 0;
-    const int gv = ((f->gather_split & 2) ? 4 : 0) | ((f->gather_split & 4) ? 12 : 0) | (half_tables ? 16 : 0);
-    SHERF_RUN(sherf_gather_tokens(imp->counters, imp->geom, f->planes_f, f->P, f->feat_f, f->Hf, f->Wf, f->img4, f->H, f->W, levels, f->tok_bias, f->bounds,
-                                  f->vox_min, f->vox_sh, 0 | gv, ftok, imp->tokens, imp->extras, stream_main));
-    if (f->mlp_prec & SHERF_MLP_OSG_DECODER)
-        SHERF_RUN(sherf_osg_decoder(imp->counters, imp->tokens, imp->extras, static_cast<const float*>(f->wstream), (f->mlp_prec & SHERF_MLP_NO_TRANSFORMER) ? 1 : 0,
-                                    ftok, imp->sample_out, stream_main));
-    else if ((f->mlp_prec & 255) != 1 && (f->flags & SHERF_FRAME_MLP_PIPELINED))
-        SHERF_RUN(sherf_nerf_mlp3(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
-    else if ((f->mlp_prec & 255) != 1 && (f->flags & SHERF_FRAME_MLP_TWO_TILES))
-        SHERF_RUN(sherf_nerf_mlp2(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
-    else
-        SHERF_RUN(sherf_nerf_mlp(imp->counters, imp->tokens, imp->extras, f->wstream, f->wbias, f->mlp_prec, ftok, imp->sample_out, stream_main));
-    return sherf_composite_merged(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, tok_cap, imp->depths_fine, imp->ray_mask, imp->ray_base,
-                                  imp->sample_out, ftok, f->ray_d, f->near, f->far, f->R, f->S, imp->n, f->white_back, f->rgb, f->depth, f->acc, stream_main);
+    SHERF_RUN(enqueue_warp(f, fine, f->ray_d, imp->n, stream_main));
+    SHERF_RUN(enqueue_gather(f, fine, levels, 0 | gather_mode(f), false, stream_main));
+    SHERF_RUN(enqueue_network(f, fine, false, false, 0, stream_main));
+    return sherf_composite_merged(f->counters, f->ray_base, f->ray_cnt, f->cs_idx, f->sample_out, coarse.tok_cap, imp->depths_fine, imp->ray_mask, imp->ray_base,
+                                  imp->sample_out, fine.tok_cap, f->ray_d, f->near, f->far, f->R, f->S, imp->n, f->white_back, f->rgb, f->depth, f->acc, stream_main);
 }
 
 extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_level* levels, sherf_stream_t stream_main,
@@ -602,20 +579,18 @@ extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_lev
         g_graph_aux_ok = ea && atoi(ea) != 0;
     }
     int dev = 0;
+    DevState* dp = nullptr;
     bool prof;
     { std::lock_guard<std::mutex> lk(g_mu); prof = g_prof_on; }
     const int xp = sherf_experiment();
     const bool eligible = g_graph_on == 1 && (phase == 1 || phase == 3) && !prof && !(f->flags & (SHERF_FRAME_EXACT_GRIDS | SHERF_FRAME_REPORT_COUNT)) &&
-                          !(xp & (16 | 32)) && f->vox_plan && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDev && g_dev[dev].init &&
+                          !(xp & (16 | 32)) && f->vox_plan && device_state(dev, dp, false) == SHERF_OK && dp->init &&
                           // MEASURED (MI355X, ROCm 7.0 runtime of PyTorch 2.10; profiles/r06_call_d_f_*): hipStreamEndCapture CRASHES on the frame's
                           // three-stream capture (main + side + aux with their cross dependencies) inside the product process, while the two-stream
                           // capture works (and the same three-stream shape works in a stand-alone probe, tools/ubench/graph_probe.hip).  Until
                           // that is understood only frames WITHOUT the third stream are captured (SHERF_FRAME_GRAPH_AUX=1 lifts the guard).
                           (!stream_aux || g_graph_aux_ok);
-    if (!eligible) {
-        ++g_graph_stats[2];
-        return render_frame_enqueue(f, phase, levels, stream_main, stream_side, stream_aux);
-    }
+    if (!eligible) return render_frame_eager(f, phase, levels, stream_main, stream_side, stream_aux);
     uint64_t key = 1469598103934665603ull;
     fnv(key, f, sizeof(*f));
     fnv(key, f->vox_plan, sizeof(*f->vox_plan));
@@ -640,21 +615,17 @@ extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_lev
     if (!slot) {                                                      // first sighting: eager, remember the key
         graph_drop(*lru);
         lru->key = key; lru->state = 1; lru->stamp = ++g_graph_clock;
-        ++g_graph_stats[2];
-        return render_frame_enqueue(f, phase, levels, stream_main, stream_side, stream_aux);
+        return render_frame_eager(f, phase, levels, stream_main, stream_side, stream_aux);
     }
     slot->stamp = ++g_graph_clock;
-    if (slot->state == 3) {
-        ++g_graph_stats[2];
-        return render_frame_enqueue(f, phase, levels, stream_main, stream_side, stream_aux);
-    }
+    if (slot->state == 3) return render_frame_eager(f, phase, levels, stream_main, stream_side, stream_aux);
     // second sighting: capture (on the library's own stream: the caller's may be the legacy default stream), instantiate, launch on the caller's
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int rc = SHERF_ELAUNCH;
     const char* stage = "stream";
     hipError_t e = hipSuccess;
-    DevState& d = g_dev[dev];
+    DevState& d = *dp;
     if (!d.cap_stream) e = hipStreamCreateWithFlags(&d.cap_stream, hipStreamNonBlocking);
     bool ok = e == hipSuccess && d.cap_stream;
     g_sherf_cap_trace = getenv("SHERF_FRAME_GRAPH_DEBUG") ? 1 : 0;
@@ -681,8 +652,8 @@ extern "C" int sherf_render_frame(const sherf_frame* f, int phase, sherf_vox_lev
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
         slot->state = 3;
-        ++g_graph_stats[3]; ++g_graph_stats[2];
-        return render_frame_enqueue(f, phase, levels, stream_main, stream_side, stream_aux);
+        ++g_graph_stats[3];
+        return render_frame_eager(f, phase, levels, stream_main, stream_side, stream_aux);
     }
     slot->graph = graph; slot->exec = exec; slot->state = 2;
     for (int i = 0; i < 3; ++i) slot->lv[i] = levels[i];

@@ -25,21 +25,7 @@
 
 namespace {
 
-enum { CLAMP_RELU = 0, CLAMP_SOFTPLUS = 1 };
-
-// (csrc/composite.hip: density / depth_at -- restated, the kernels there live in an anonymous namespace)
-template <int MODE>
-__device__ __forceinline__ float density(float sigma) {
-    if (MODE == CLAMP_RELU) return fmaxf(sigma, 0.f);
-    const float x = sigma - 1.f;
-    return x > 20.f ? x : log1pf(expf(x));
-}
-
-__device__ __forceinline__ float depth_at(float near, float range, int k, int S) {
-    float step = __fdiv_rn((float)k, (float)(S - 1));
-    return __fadd_rn(near, __fmul_rn(step, range));
-}
-
+// (density<MODE> / depth_at: the compositing's, csrc/passes.h)
 constexpr int kMaxS = 256, kMaxN = 256;
 
 template <int MODE>

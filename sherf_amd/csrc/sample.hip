@@ -290,14 +290,8 @@ __global__ void __launch_bounds__(256) near_lists_alloc_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-// pass 1: one wave per ray: depths, positions, exact NN within 5 cm, validity mask
+// pass 1: one wave per ray: depths, positions, exact NN within 5 cm, validity mask (depth_at: csrc/passes.h)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float depth_at(float near, float range, int k, int S) {
-    // math_utils.py:101-118: steps = arange(S)/(S-1);  t = near + steps * (far - near)
-    float step = __fdiv_rn((float)k, (float)(S - 1));
-    return __fadd_rn(near, __fmul_rn(step, range));
-}
-
 // One wave per ray.  Candidate samples (near-mask hit: ~12 % of the samples, ~30 on a ray that crosses the body) are searched by
 // EIGHT-LANE GROUPS, eight candidates at a time: each candidate lane first fetches the nine x-contiguous point segments of its
 // 3x3x3 cell neighbourhood, trimmed to the cells its 5 cm ball reaches (18 independent loads, all candidates in parallel), and parks
@@ -1287,15 +1281,6 @@ __global__ void __launch_bounds__(256) warp_geom_kernel(const int32_t* __restric
 
 }  // namespace
 
-int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const float* near, const float* far, int R, int S, const float* Rg, const float* Th,
-                              const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
-                              int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx, int32_t* cs_vid, float* cs_xs, int32_t* dense_vid,
-                              uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky,
-                              int32_t* cell_ws, int64_t cell_ws_len);
-int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
-                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
-                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream);
-
 extern "C" int sherf_build_cells(const float* verts, int n, const float* R, const float* Th, float cell_size,
                                  float* grid_hdr, int32_t* cell_start, float* cell_pts, int32_t* scratch,
                                  uint32_t* near_mask, sherf_stream_t stream) {
@@ -1349,8 +1334,8 @@ extern "C" int sherf_sample_mask_nn(const float* ray_o, const float* ray_d, cons
                                     int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
                                        int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
                                        int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream) {
-    return sherf_sample_mask_nn_impl(ray_o, ray_d, near, far, R, S, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt,
-                                     cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr, nullptr, 0);
+    return sherf_sample_mask_nn_ws(ray_o, ray_d, near, far, R, S, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt,
+                                   cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, nullptr, 0, stream);
 }
 
 // sherf_sample_mask_nn with the workspace of the search by sub-cell (include/sherf_hip.h)
@@ -1361,8 +1346,9 @@ extern "C" int sherf_sample_mask_nn_ws(const float* ray_o, const float* ray_d, c
                                        int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
                                        int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, int32_t* cell_ws, int64_t cell_ws_len,
                                        sherf_stream_t stream) {
-    return sherf_sample_mask_nn_impl(ray_o, ray_d, near, far, R, S, Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, capacity, counters, ray_base, ray_cnt,
-                                     cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, near_hdr, near_list, stream, nullptr, cell_ws, cell_ws_len);
+    return sherf_sample_mask_nn_impl({ray_o, ray_d, near, far, R, S}, {Rg, Th, grid_hdr, cell_start, cell_pts, near_mask, near_hdr, near_list},
+                                     {counters, ray_base, ray_cnt, cs_idx, cs_vid, cs_xs, dense_vid, ray_mask, scan_ws, capacity}, stream, nullptr, cell_ws,
+                                     cell_ws_len);       // (the token side of the pass stays empty: the sampler does not look at it)
 }
 
 // Pass 2 of the two-pass sampler and the first scan kernel, on the candidate list some pass 1 left in `cand_list` (records (x_s, dense index), index = row * S + k):
@@ -1398,72 +1384,66 @@ static void search_and_scan(hipStream_t st, int R, int S, const float* grid_hdr,
     hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(cdiv(R, 1024)), dim3(1024), 0, st, ray_mask, R, ray_cnt, base_local, chunk_sum);
 }
 
-// The point sampler's use of this file's machinery (csrc/field.hip: sherf_points_mask_nn_impl; `rows` rows of 64 points).  _begin resets the counters and the
-// candidate count ahead of point_mark_kernel; _search runs the candidate search and both scan kernels behind it: counters[0] = the valid points.
+// The point sampler's use of this file's machinery (csrc/field.hip: sherf_points_mask_nn_impl; csrc/passes.h)
 int sherf_points_begin_impl(int32_t* counters, int32_t* scan_ws, int rows, int32_t* sticky, sherf_stream_t stream) {
     hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream), counters, sherf_scan_ws(scan_ws, rows).cand_count, sticky, static_cast<int32_t*>(nullptr));
     SHERF_LAUNCH_CHECK();
 }
-int sherf_points_search_impl(int rows, const float* grid_hdr, const int32_t* cell_start, const float* cell_pts, const float* cand_list, int64_t list_cap,
-                             int32_t* counters, int32_t* ray_cnt, int32_t* dense_vid, uint64_t* ray_mask, int32_t* scan_ws, const int32_t* near_hdr,
-                             const uint16_t* near_list, sherf_stream_t stream) {
-    const SherfScanWs w = sherf_scan_ws(scan_ws, rows);
-    search_and_scan<1>(as_stream(stream), rows, 64, grid_hdr, cell_start, reinterpret_cast<const float4*>(cell_pts), reinterpret_cast<const float4*>(cand_list),
-                       list_cap, w.cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, w.base_local, w.chunk_sum);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.chunk_sum, cdiv(rows, 1024), counters);
+int sherf_points_search_impl(int rows, const SherfBodyIndex& bi, const SherfSamples& s, sherf_stream_t stream) {
+    const SherfScanWs w = sherf_scan_ws(s.scan_ws, rows);
+    search_and_scan<1>(as_stream(stream), rows, 64, bi.grid_hdr, bi.cell_start, reinterpret_cast<const float4*>(bi.cell_pts), reinterpret_cast<const float4*>(s.cs_xs),
+                       s.capacity, w.cand_count, bi.near_hdr, bi.near_list, s.dense_vid, s.ray_mask, s.ray_cnt, w.base_local, w.chunk_sum);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.chunk_sum, cdiv(rows, 1024), s.counters);
     SHERF_LAUNCH_CHECK();
 }
 
-// (the frame driver's entry: `sticky`, see init_counters_kernel)
-int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const float* near, const float* far,
-                              int R, int S, const float* Rg, const float* Th, const float* grid_hdr,
-                              const int32_t* cell_start, const float* cell_pts, const uint32_t* near_mask, int64_t capacity,
-                              int32_t* counters, int32_t* ray_base, int32_t* ray_cnt, int32_t* cs_idx,
-                              int32_t* cs_vid, float* cs_xs, int32_t* dense_vid, uint64_t* ray_mask,
-                              int32_t* scan_ws, const int32_t* near_hdr, const uint16_t* near_list, sherf_stream_t stream, int32_t* sticky,
+int sherf_sample_mask_nn_impl(const SherfRays& rays, const SherfBodyIndex& bi, const SherfSamples& s, sherf_stream_t stream, int32_t* sticky,
                               int32_t* cell_ws, int64_t cell_ws_len) {
-    SHERF_CHECK_ARG(ray_o && ray_d && near && far && Rg && Th && grid_hdr && cell_start && cell_pts && near_mask);
-    SHERF_CHECK_ARG(cell_ws == nullptr || (cell_ws_len >= SHERF_CELL_WS_INTS(R, S) && (reinterpret_cast<uintptr_t>(cell_ws) & 7) == 0));
-    SHERF_CHECK_ARG(counters && ray_base && ray_cnt && cs_idx && cs_vid && cs_xs && dense_vid && ray_mask && scan_ws);
-    SHERF_CHECK_ARG(R > 0 && S >= 2 && S <= 256 && (int64_t)R * S < 2147483647LL && capacity > 0 && (near_hdr == nullptr) == (near_list == nullptr));
+    SHERF_CHECK_ARG(rays.o && rays.d && rays.near && rays.far && bi.Rg && bi.Th && bi.grid_hdr && bi.cell_start && bi.cell_pts && bi.near_mask);
+    SHERF_CHECK_ARG(cell_ws == nullptr || (cell_ws_len >= SHERF_CELL_WS_INTS(rays.R, rays.S) && (reinterpret_cast<uintptr_t>(cell_ws) & 7) == 0));
+    SHERF_CHECK_ARG(s.counters && s.ray_base && s.ray_cnt && s.cs_idx && s.cs_vid && s.cs_xs && s.dense_vid && s.ray_mask && s.scan_ws);
+    SHERF_CHECK_ARG(rays.R > 0 && rays.S >= 2 && rays.S <= 256 && (int64_t)rays.R * rays.S < 2147483647LL && s.capacity > 0 &&
+                    (bi.near_hdr == nullptr) == (bi.near_list == nullptr));
+    const int R = rays.R, S = rays.S;
+    const int64_t capacity = s.capacity;
     hipStream_t st = as_stream(stream);
     const int nch = (S + 63) / 64;
     const int n_chunks = cdiv(R, 1024);
-    const SherfScanWs sw = sherf_scan_ws(scan_ws, R);
+    const SherfScanWs sw = sherf_scan_ws(s.scan_ws, R);
     int32_t* base_local = sw.base_local;        // [R]
     int32_t* chunk_sum = sw.chunk_sum;          // [n_chunks]
-    const float4* cp = reinterpret_cast<const float4*>(cell_pts);
+    const float4* cp = reinterpret_cast<const float4*>(bi.cell_pts);
     int32_t* cand_count = sw.cand_count;
     // two passes over a dense candidate list (see cand_mark_kernel) whenever the list -- `capacity` records in cs_xs, which the
     // compaction below only writes afterwards -- provably holds every sample; sherf_set_debug bit 9 forces the one-wave-per-ray kernel
     const bool two_pass = !(g_sherf_debug & 512) && capacity >= (int64_t)R * S;
     // the search by sub-cell (cand_search_cells_kernel) wherever its workspace and the near lists are there; sherf_set_debug bit 28 keeps the search
     // by candidate (cand_search_lists_kernel) for A/B runs, as do the bits that select one of its variants
-    const bool cells = two_pass && cell_ws && near_hdr && near_list && !(g_sherf_debug & (16384 | kDebugSearchByCandidate)) && !(sherf_experiment() & 16384);
+    const bool cells = two_pass && cell_ws && bi.near_hdr && bi.near_list && !(g_sherf_debug & (16384 | kDebugSearchByCandidate)) && !(sherf_experiment() & 16384);
     const SherfCellWs cw = sherf_cell_ws(cell_ws, R, S);
-    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, st, counters, cand_count, sticky, cells ? cw.cursors : static_cast<int32_t*>(nullptr));
-    hipLaunchKernelGGL(depth_minmax_kernel, dim3(min(256, cdiv(R, 256))), dim3(256), 0, st, near, far, R, S, counters);
+    hipLaunchKernelGGL(init_counters_kernel, dim3(1), dim3(1), 0, st, s.counters, cand_count, sticky, cells ? cw.cursors : static_cast<int32_t*>(nullptr));
+    hipLaunchKernelGGL(depth_minmax_kernel, dim3(min(256, cdiv(R, 256))), dim3(256), 0, st, rays.near, rays.far, R, S, s.counters);
     if (two_pass) {
-        float4* cand_list = reinterpret_cast<float4*>(cs_xs);            // one 16-byte record per candidate: the list holds `capacity` of them
+        float4* cand_list = reinterpret_cast<float4*>(s.cs_xs);            // one 16-byte record per candidate: the list holds `capacity` of them
         const int64_t list_cap = capacity;
         int32_t* const no_i32 = nullptr;
         // workgroups per CU of the persistent search by sub-cell (debug bits 20-23 override, as for the search by candidate)
         const int cells_wgs = ((g_sherf_debug >> 20) & 15) ? ((g_sherf_debug >> 20) & 15) : kCellSearchWgs;
 #define SHERF_TWO_PASS(N)                                                                                                          \
         if (cells) {                                                                                                               \
-            hipLaunchKernelGGL((cand_mark_kernel<N, true>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
-                               grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug, cw.sub_cnt, cs_idx, cs_vid); \
-            hipLaunchKernelGGL(cand_cells_alloc_kernel, dim3(SHERF_NEAR_SUBCELLS / 256), dim3(256), 0, st, grid_hdr, cw.sub_cnt, cw.sub_off, cw.cursors, \
+            hipLaunchKernelGGL((cand_mark_kernel<N, true>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th, \
+                               bi.grid_hdr, bi.near_mask, cand_list, list_cap, cand_count, s.ray_mask, g_sherf_debug, cw.sub_cnt, s.cs_idx, s.cs_vid); \
+            hipLaunchKernelGGL(cand_cells_alloc_kernel, dim3(SHERF_NEAR_SUBCELLS / 256), dim3(256), 0, st, bi.grid_hdr, cw.sub_cnt, cw.sub_off, cw.cursors, \
                                cw.items, cw.item_cap, list_cap);                                                                   \
-            hipLaunchKernelGGL(cand_place_kernel, dim3(min(8 * n_cus(), cdiv((int64_t)R * S, 256))), dim3(256), 0, st, ray_o, ray_d, near, far, S, Rg, Th, \
-                               grid_hdr, cs_idx, cs_vid, cand_count, cw.sub_off, cand_list, list_cap);                             \
+            hipLaunchKernelGGL(cand_place_kernel, dim3(min(8 * n_cus(), cdiv((int64_t)R * S, 256))), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, S, bi.Rg, bi.Th, \
+                               bi.grid_hdr, s.cs_idx, s.cs_vid, cand_count, cw.sub_off, cand_list, list_cap);                             \
             hipLaunchKernelGGL(cand_search_cells_kernel<N>, dim3(cells_wgs * n_cus()), dim3(256), 0, st, cand_list, cw.items, cw.cursors, cw.item_cap, S, \
-                               reinterpret_cast<const int2*>(near_hdr), near_list, cp, reinterpret_cast<unsigned long long*>(ray_mask), dense_vid); \
-            hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(cdiv(R, 1024)), dim3(1024), 0, st, ray_mask, R, ray_cnt, base_local, chunk_sum); \
+                               reinterpret_cast<const int2*>(bi.near_hdr), bi.near_list, cp, reinterpret_cast<unsigned long long*>(s.ray_mask), s.dense_vid); \
+            hipLaunchKernelGGL(scan_chunk_mask_kernel<N>, dim3(cdiv(R, 1024)), dim3(1024), 0, st, s.ray_mask, R, s.ray_cnt, base_local, chunk_sum); \
         } else {                                                                                                                   \
-            hipLaunchKernelGGL((cand_mark_kernel<N, false>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
-                               grid_hdr, near_mask, cand_list, list_cap, cand_count, ray_mask, g_sherf_debug, no_i32, no_i32, no_i32); \
-            search_and_scan<N>(st, R, S, grid_hdr, cell_start, cp, cand_list, list_cap, cand_count, near_hdr, near_list, dense_vid, ray_mask, ray_cnt, base_local, \
+            hipLaunchKernelGGL((cand_mark_kernel<N, false>), dim3(cdiv(R, 4 * (16 / N))), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th, \
+                               bi.grid_hdr, bi.near_mask, cand_list, list_cap, cand_count, s.ray_mask, g_sherf_debug, no_i32, no_i32, no_i32); \
+            search_and_scan<N>(st, R, S, bi.grid_hdr, bi.cell_start, cp, cand_list, list_cap, cand_count, bi.near_hdr, bi.near_list, s.dense_vid, s.ray_mask, s.ray_cnt, base_local, \
                                chunk_sum);                                                                                         \
         }
         if (nch == 1) { SHERF_TWO_PASS(1) } else if (nch == 2) { SHERF_TWO_PASS(2) } else if (nch == 3) { SHERF_TWO_PASS(3) } else { SHERF_TWO_PASS(4) }
@@ -1475,25 +1455,25 @@ int sherf_sample_mask_nn_impl(const float* ray_o, const float* ray_d, const floa
     // profiles/r02_sconv_sampler_balance.txt).
     constexpr int nn_pad = 10 * 1024;
 #define SHERF_SAMPLE_LAUNCH(N)                                                                                        \
-    hipLaunchKernelGGL(sample_nn_kernel<N>, dim3(cdiv(R, 4)), dim3(256), nn_pad, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
-                       grid_hdr, cell_start, cp, near_mask, ray_cnt, ray_mask, dense_vid, g_sherf_debug)
+    hipLaunchKernelGGL(sample_nn_kernel<N>, dim3(cdiv(R, 4)), dim3(256), nn_pad, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th, \
+                       bi.grid_hdr, bi.cell_start, cp, bi.near_mask, s.ray_cnt, s.ray_mask, s.dense_vid, g_sherf_debug)
     if (nch == 1) SHERF_SAMPLE_LAUNCH(1); else if (nch == 2) SHERF_SAMPLE_LAUNCH(2);
     else if (nch == 3) SHERF_SAMPLE_LAUNCH(3); else SHERF_SAMPLE_LAUNCH(4);
-    hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_chunks), dim3(1024), 0, st, ray_cnt, R, base_local, chunk_sum);
+    hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_chunks), dim3(1024), 0, st, s.ray_cnt, R, base_local, chunk_sum);
     }
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, st, chunk_sum, n_chunks, counters);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, st, chunk_sum, n_chunks, s.counters);
 #define SHERF_COMPACT_LAUNCH(N)                                                                                        \
-    hipLaunchKernelGGL(compact_kernel<N>, dim3(cdiv(R, 4)), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th,   \
-                       base_local, chunk_sum, ray_mask, dense_vid, capacity, ray_base, cs_idx, cs_vid,                 \
-                       reinterpret_cast<float4*>(cs_xs), cp)
+    hipLaunchKernelGGL(compact_kernel<N>, dim3(cdiv(R, 4)), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th,   \
+                       base_local, chunk_sum, s.ray_mask, s.dense_vid, capacity, s.ray_base, s.cs_idx, s.cs_vid,                 \
+                       reinterpret_cast<float4*>(s.cs_xs), cp)
 #define SHERF_COMPACT_RAYS_LAUNCH(N)                                                                                   \
-    hipLaunchKernelGGL(compact_rays_kernel<N>, dim3(cdiv(R, 256)), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
-                       base_local, chunk_sum, ray_mask, dense_vid, capacity, ray_base, cs_idx, cs_vid,                 \
-                       reinterpret_cast<float4*>(cs_xs))
+    hipLaunchKernelGGL(compact_rays_kernel<N>, dim3(cdiv(R, 256)), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th, \
+                       base_local, chunk_sum, s.ray_mask, s.dense_vid, capacity, s.ray_base, s.cs_idx, s.cs_vid,                 \
+                       reinterpret_cast<float4*>(s.cs_xs))
 #define SHERF_COMPACT_QUAD_LAUNCH(N)                                                                                   \
-    hipLaunchKernelGGL(compact_quad_kernel<N>, dim3(cdiv(R, 16)), dim3(256), 0, st, ray_o, ray_d, near, far, R, S, Rg, Th, \
-                       base_local, chunk_sum, ray_mask, dense_vid, capacity, ray_base, cs_idx, cs_vid,                 \
-                       reinterpret_cast<float4*>(cs_xs))
+    hipLaunchKernelGGL(compact_quad_kernel<N>, dim3(cdiv(R, 16)), dim3(256), 0, st, rays.o, rays.d, rays.near, rays.far, R, S, bi.Rg, bi.Th, \
+                       base_local, chunk_sum, s.ray_mask, s.dense_vid, capacity, s.ray_base, s.cs_idx, s.cs_vid,                 \
+                       reinterpret_cast<float4*>(s.cs_xs))
     if ((sherf_experiment() & 8192) && nch != 3) {      // SHERF_EXPERIMENT bit 13: sixteen lanes per ray (round 6)
         if (nch == 1) SHERF_COMPACT_QUAD_LAUNCH(1); else if (nch == 2) SHERF_COMPACT_QUAD_LAUNCH(2); else SHERF_COMPACT_QUAD_LAUNCH(4);
     } else
@@ -1513,22 +1493,24 @@ extern "C" int sherf_warp_geom(const int32_t* counters, const int32_t* cs_idx, c
                                const int32_t* tcell_start, const float* tcell_pts, int64_t capacity, float* geom,
                                int32_t* cs_tvid, sherf_stream_t stream) {
     SHERF_CHECK_ARG(S >= 2);
-    return sherf_warp_geom_impl(counters, cs_idx, cs_vid, cs_xs, ray_d, S, Rg, T2C, C2S, t_verts, tgrid_hdr, tcell_start, tcell_pts, capacity, geom, cs_tvid, stream);
+    SherfBodyIndex target = {};
+    target.Rg = Rg; target.grid_hdr = tgrid_hdr; target.cell_start = tcell_start; target.cell_pts = tcell_pts;
+    SherfSamples s = {};        // (the sampler's records are read only here)
+    s.counters = const_cast<int32_t*>(counters); s.cs_idx = const_cast<int32_t*>(cs_idx); s.cs_vid = const_cast<int32_t*>(cs_vid);
+    s.cs_xs = const_cast<float*>(cs_xs); s.geom = geom; s.cs_tvid = cs_tvid; s.tok_cap = capacity;
+    return sherf_warp_geom_impl(target, T2C, C2S, t_verts, s, stream, ray_d, S);
 }
 
-// `dir_stride`: how many consecutive dense indices share one row of `dirs` -- S for a frame's rays (the exported entry point, which refuses S < 2), 1 for the
-// field query's per-point view directions (csrc/frame.hip: dirs[cs_idx[c]]).  The kernel divides cs_idx by it either way.
-int sherf_warp_geom_impl(const int32_t* counters, const int32_t* cs_idx, const int32_t* cs_vid, const float* cs_xs, const float* ray_d, int S, const float* Rg,
-                         const float* T2C, const float* C2S, const float* t_verts, const float* tgrid_hdr, const int32_t* tcell_start, const float* tcell_pts,
-                         int64_t capacity, float* geom, int32_t* cs_tvid, sherf_stream_t stream) {
-    SHERF_CHECK_ARG(counters && cs_idx && cs_vid && cs_xs && ray_d && Rg && T2C && C2S && t_verts && tgrid_hdr &&
-                    tcell_start && tcell_pts && geom && cs_tvid);
-    SHERF_CHECK_ARG(S >= 1 && capacity > 0);
+int sherf_warp_geom_impl(const SherfBodyIndex& target, const float* T2C, const float* C2S, const float* t_verts, const SherfSamples& s, sherf_stream_t stream,
+                         const float* dirs, int dir_stride) {
+    SHERF_CHECK_ARG(s.counters && s.cs_idx && s.cs_vid && s.cs_xs && dirs && target.Rg && T2C && C2S && t_verts && target.grid_hdr &&
+                    target.cell_start && target.cell_pts && s.geom && s.cs_tvid);
+    SHERF_CHECK_ARG(dir_stride >= 1 && s.tok_cap > 0);
     // (SHERF_EXPERIMENT bits 16-19, round 6: w persistent workgroups per CU instead of one per 256 samples -- room for the encoder's big-register waves beside it)
     const int warp_wgs = (sherf_experiment() >> 16) & 15;
-    const int warp_grid = warp_wgs ? min(warp_wgs * n_cus(), cdiv(capacity, 256)) : min(8192, cdiv(capacity, 256));
-    hipLaunchKernelGGL(warp_geom_kernel, dim3(warp_grid), dim3(256), 0, as_stream(stream), counters, cs_idx,
-                       cs_vid, reinterpret_cast<const float4*>(cs_xs), ray_d, S, Rg, T2C, C2S, t_verts, tgrid_hdr,
-                       tcell_start, reinterpret_cast<const float4*>(tcell_pts), capacity, geom, cs_tvid);
+    const int warp_grid = warp_wgs ? min(warp_wgs * n_cus(), cdiv(s.tok_cap, 256)) : min(8192, cdiv(s.tok_cap, 256));
+    hipLaunchKernelGGL(warp_geom_kernel, dim3(warp_grid), dim3(256), 0, as_stream(stream), s.counters, s.cs_idx,
+                       s.cs_vid, reinterpret_cast<const float4*>(s.cs_xs), dirs, dir_stride, target.Rg, T2C, C2S, t_verts, target.grid_hdr,
+                       target.cell_start, reinterpret_cast<const float4*>(target.cell_pts), s.tok_cap, s.geom, s.cs_tvid);
     SHERF_LAUNCH_CHECK();
 }
